@@ -26,19 +26,31 @@ line is c3):
       (k = 32), aggregation (all-gather + server solve + broadcast) every 64
       batches; one step = 64 batches + one aggregation.
 
-Extra objects on the JSON line: ``roofline`` (the dominant kernel vs the peak of
-the instructions it runs, timed with HIP events on the launch stream),
+A plain run sets up, warms up, times the K steps and prints the JSON line:
+``roofline`` (the dominant kernel vs the peak of the instructions it runs, from
+the HIP events the timed steps record on the launch stream), ``breakdown`` and
+the solver residuals in ``accuracy`` come from the timed steps themselves.
+``--full`` adds everything that takes runs of its own, after the timed steps:
 ``sweep`` (one subspace-iteration sweep S*Q vs the HBM roof, both sweep
 kernels), ``cpu_baseline`` (the float64 oracle on a bounded sample of the same
-workload, rank 0 at N = 1 only), ``breakdown`` and ``accuracy``.
+workload, rank 0 at N = 1 only), the float64 checks in ``accuracy``,
+``roofline.fp32_kernel`` and c3's ``time_to_eigenspace_16M_rows_1gpu``; the
+``--no-*`` switches drop single legs of it.
+
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0) as
+DIR/<name>.npy, float32: the gathered worker bases, the last worker's
+eigenvalues and covariance, the server's basis and eigenvalues (one-shot
+configs) or the Oja basis (c4).  An array above 8 MiB is stored as a fixed,
+seeded sample of its entries (dump_outputs).  The inputs are seeded, so two
+runs with the same arguments compute from identical data.
 
 Covariance algorithm (--syrk-algo, default auto = split3 at these sizes): fp32
 samples split into bf16 hi/lo pairs, 3 bf16 MFMA products per fp32 product,
-fp32 accumulation (include/deig.h); "fp32" = the f32 MFMA kernel.  The fp32
-kernel is also timed once outside the timed region (``roofline.fp32_kernel``).
+fp32 accumulation (include/deig.h); "fp32" = the f32 MFMA kernel.  With --full the
+fp32 kernel is also timed once outside the timed region (``roofline.fp32_kernel``).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1|c1g|c4|c5]
-       [--syrk-algo auto|split3|fp32]
+       [--syrk-algo auto|split3|fp32] [--full] [--dump-outputs DIR]
        (N > 1: either under python -m torch.distributed.run --nproc-per-node N, or
        plain ``python bench.py --gpus N``, which starts the N ranks itself)
 """
@@ -310,6 +322,23 @@ def cpu_baseline_oja(pool, V0: torch.Tensor, eta: float, nb: int):
         "sample": (f"float64 NumPy oracle oja_epoch on {nb} batches of {b} x {xs.shape[1]} "
                    f"(k={V0.shape[1]}): {t:.2f}s; aggregation not counted"),
     }
+
+
+DUMP_MAX_BYTES = 8 << 20  # per array; at most 6 arrays per config: 48 MiB of the 64 MB allowed
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """Write each array as ``path/<name>.npy`` in float32.  An array above DUMP_MAX_BYTES
+    is stored as DUMP_MAX_BYTES / 4 of its entries (row-major order) at fixed positions:
+    sorted draws of numpy's default_rng(0), the same for every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach()
+        keep = DUMP_MAX_BYTES // 4
+        if a.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.numel(), size=keep))
+            a = a.contiguous().reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
 
 
 def sin_theta(U: torch.Tensor, V: torch.Tensor) -> float:
@@ -608,6 +637,7 @@ def base_line(args, world, elapsed, total, dtype, config):
         "process_group": formed_group(args),
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "step_ms": dict(STEP_MS),
         "higher_is_better": True,
@@ -769,7 +799,15 @@ def run_oneshot(args, cfg, world, rank, dev):
 
     elapsed, (r, res) = timed_loop(step, args, world, dev)
 
-    syrk_ms = float(np.mean([a.elapsed_time(b) for (a, b), _ in syrk_ev]))
+    # the last worker's covariance (Ss[0] is S = worker 0's in the concurrent and
+    # batched modes)
+    S_last = Ss[-1] if (concurrent or batched) else S
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "worker_bases": Wt_local, "last_worker_evals": r.evals, "last_worker_sigma_hat": S_last,
+            "server_V": res.V, "server_evals": res.evals})
+
+    syrk_ms =float(np.mean([a.elapsed_time(b) for (a, b), _ in syrk_ev]))
     sweeps = [s for _, s in syrk_ev]
     flops = float(ni) * d * (d + 1)  # algorithmic, per worker launch: lower triangle incl. diag
     algo = args.syrk_algo
@@ -801,26 +839,25 @@ def run_oneshot(args, cfg, world, rank, dev):
     # concurrent workers: the in-loop events also span other workers' solve kernels
     # interleaved on their side streams, so the covariance is also timed alone
     syrk_alone_ms = None
-    if concurrent:
+    if concurrent and args.full:
         syrk_alone_ms = time_events(lambda: de.sigma_hat(X[:ni], out=S, algo=args.syrk_algo),
                                     5, stream)
 
-    # --- outside the timed region: accuracy, alternative kernel, sweep roofline
+    # --- outside the timed region, --full only: accuracy, alternative kernel, sweep roofline
     if concurrent or batched:
         del Ss[1:-1]  # keep worker 0's (S, reused below) and the last worker's buffer
         torch.cuda.empty_cache()
     Xw = X[(W - 1) * ni:W * ni]
-    cols = torch.randperm(d, generator=torch.Generator().manual_seed(7))[:16].to(dev)
-    Xs = features(Xw).index_select(1, cols)
-    S64 = (Xs.t() @ Xs) / ni
-    # the last worker's covariance (Ss[0] is S = worker 0's in the concurrent and
-    # batched modes; r03y and before compared it with the last worker's rows there)
-    S_last = Ss[-1] if (concurrent or batched) else S
-    Sblk = S_last.index_select(0, cols).index_select(1, cols).double()
-    sigma_err = float((Sblk - S64).abs().max() / S64.abs().max())
-    del Xs
+    sigma_err = None
+    if args.full:
+        cols = torch.randperm(d, generator=torch.Generator().manual_seed(7))[:16].to(dev)
+        Xs = features(Xw).index_select(1, cols)
+        S64 = (Xs.t() @ Xs) / ni
+        Sblk = S_last.index_select(0, cols).index_select(1, cols).double()
+        sigma_err = float((Sblk - S64).abs().max() / S64.abs().max())
+        del Xs
     fp32_kernel = None
-    if algo == "split3" and not args.no_alt:
+    if args.full and algo == "split3" and not args.no_alt:
         S2 = torch.empty_like(S)
         ms = time_events(lambda: de.sigma_hat(Xw, out=S2, algo="fp32"), 1, stream)
         fp32_kernel = {"kernel": "syrk_kernel (+ syrk_reduce_kernel), v_mfma_f32_32x32x2_f32",
@@ -831,10 +868,10 @@ def run_oneshot(args, cfg, world, rank, dev):
                                                            / S_last.abs().max())}
         del S2
     p = de.default_subspace(d, k)
-    sweep = sweep_roofline(de, S, p, stream)
+    sweep = sweep_roofline(de, S, p, stream) if args.full else None
 
     acc_u8 = None
-    if u8 and rank == 0:
+    if args.full and u8 and rank == 0:
         # bytes: the covariance is exact, so the last worker's basis is checked
         # against float64 eigh of the same shard (the planted U is not the top-k of
         # an uncentered byte covariance: its mean direction dominates)
@@ -871,11 +908,11 @@ def run_oneshot(args, cfg, world, rank, dev):
         except Exception as e:  # pragma: no cover
             traffic_note = f"unreadable ({e})"
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_oneshot(features(X[:min(args.cpu_sample, ni)]).cpu().numpy(),
                                    ni, W, k)
     full = None
-    if cfg.get("full_rows") and world == 1 and not args.rows and not args.no_full:
+    if args.full and cfg.get("full_rows") and world == 1 and not args.rows and not args.no_full:
         full = full_time_to_eigenspace(de, spiked_block_fn(synthetic, U), X[:ni], U,
                                        cfg["full_rows"], k, stream)
     line = base_line(args, world, elapsed, float(n) * world * args.steps, "u8" if u8 else "f32", {
@@ -924,8 +961,9 @@ def run_oneshot(args, cfg, world, rank, dev):
                          "gather_ms": 1e3 * float(np.mean(rec["gather"])),
                          "server_ms": 1e3 * float(np.mean(rec["server"])),
                          "server_sweeps": res.sweeps}
-    line["accuracy"] = {"sin_theta_server_vs_planted": None if u8 else sin_theta(U, res.V),
-                        "sin_theta_last_worker_vs_planted": None if u8 else sin_theta(U, r.V),
+    planted = args.full and not u8
+    line["accuracy"] = {"sin_theta_server_vs_planted": sin_theta(U, res.V) if planted else None,
+                        "sin_theta_last_worker_vs_planted": sin_theta(U, r.V) if planted else None,
                         "worker_resid": r.resid, "server_resid": res.resid,
                         "sigma_hat_rel_err_vs_f64_sampled": sigma_err}
     if acc_u8:
@@ -967,6 +1005,8 @@ def run_oja(args, cfg, world, rank, dev):
         return None
 
     elapsed, _ = timed_loop(step, args, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"V": est.V})
     oja_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev])) / agg  # per batch
     # the aggregation (gather + server solve + broadcast) on the device timeline, from
     # the last Oja batch's end (r03's host clock started when the 64 batches were
@@ -980,7 +1020,7 @@ def run_oja(args, cfg, world, rank, dev):
     if rank != 0:
         return None
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_oja([pool[i * b:(i + 1) * b] for i in range(16)], V0, eta, 16)
     line = base_line(args, world, elapsed, float(agg * b) * world * args.steps, "f32", {
         "workload": cfg["label"], "batch_rows": b, "d": d, "k": k, "agg_every": agg, "eta": eta,
@@ -1011,7 +1051,7 @@ def run_oja(args, cfg, world, rank, dev):
     line["breakdown"] = {"oja_ms_per_batch": oja_ms,
                          "aggregate_ms": agg_ms,
                          "aggregate_timing": "HIP events: end of the 64th Oja batch -> end of the aggregation (all-gather + server solve + broadcast), on the launch stream"}
-    line["accuracy"] = {"sin_theta_vs_planted": sin_theta(U, est.V),
+    line["accuracy"] = {"sin_theta_vs_planted": sin_theta(U, est.V) if args.full else None,
                         "batches_seen_per_gpu": est.batches_seen}
     return line
 
@@ -1024,11 +1064,19 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU (batch rows for c4)")
     ap.add_argument("--eta", type=float, default=0.0, help="c4 step size (default: config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: CPU baseline, "
+                         "float64 accuracy checks, fp32-kernel comparison, sweep roofline, c3's "
+                         "16M-row time-to-eigenspace")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-sample", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the fp32-kernel comparison launch")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true",
+                    help="--full: skip the fp32-kernel comparison launch")
     ap.add_argument("--no-full", action="store_true",
-                    help="c3: skip streaming all 2^24 rows through one GPU (time_to_eigenspace)")
+                    help="--full, c3: skip streaming all 2^24 rows through one GPU "
+                         "(time_to_eigenspace)")
     ap.add_argument("--serial-workers", action="store_true",
                     help="W > 1 workers per GPU: run each worker's solve after its covariance on "
                          "one stream (default: one batched solve, deig_topk_sym_batch)")

@@ -15,11 +15,11 @@ tail -4 $OUT/gputests.log
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -2 $OUT/smoke.log
-timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err \
+timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err \
   || { echo "driver bench failed"; tail -20 $OUT/bench_driver.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench_driver.json')); print('c3', round(d['value']/1e6,3), d['step_ms']['median'], d['roofline']['frac'], d['roofline']['launch_ms'])"
 for c in c1 c1g c2 c4 c5; do
-  timeout -k 10 400 python -u bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err \
+  timeout -k 10 400 python -u bench.py --config $c --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err \
     || { echo "bench $c failed"; tail -20 $OUT/bench_$c.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/bench_$c.json')); print('$c', round(d['value']/1e6,3), d['step_ms']['median'], d['roofline']['frac'])"
 done

@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp
 if [ -z "$SKIP_TRACE" ]; then
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o p -- \
-  python3 $R/bench.py --no-cpu-baseline --no-alt > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err \
+  python3 $R/bench.py --full --no-cpu-baseline --no-alt > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err \
   || { echo "trace pass failed rc=$?"; tail -20 $OUT/bench_under_rocprof.err; exit 1; }
 fi
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o p -- \
