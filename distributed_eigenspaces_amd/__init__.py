@@ -6,6 +6,8 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
   * sym_apply      - one solver sweep S Q (split-bf16 MFMA)
   * sym_power      - the solver's chain of sweeps with fused power steps
   * projavg_topk   - implicit projector-average solve         (distributed.py:126-130, NB:306)
+  * procrustes_average - Procrustes-aligned basis average (one-pass aggregator, no eigensolve)
+  * subspace_distance / projector_distance - residual-form sin Theta on the device
   * oja_step(s)    - mini-batch Oja (online variant, config 4); streaming.StreamingOja
                      adds the periodic all-gather / server solve / broadcast
 
@@ -13,7 +15,8 @@ Drop-in modules: ``distributed`` (Node / SlaveNode / MasterNode / run_* / main),
 ``my_threading`` (Slave) and ``notebook`` (make_batches, top_k_eigenvectors,
 compute_segma_hat, online loop).
 """
-from .linalg import (EigResult, default_subspace, oja_step, oja_steps, projavg_topk,  # noqa: F401
-                     sigma_hat, stack_bases, sym_apply, sym_power, topk_eigh, topk_eigh_batch)
+from .linalg import (EigResult, default_subspace, oja_step, oja_steps, procrustes_average,  # noqa: F401
+                     projavg_topk, projector_distance, sigma_hat, stack_bases, subspace_distance,
+                     sym_apply, sym_power, topk_eigh, topk_eigh_batch)
 
 __version__ = "0.1.0"

@@ -156,6 +156,13 @@ SIGNATURES = {
                                             _c_i64, _c_i64, _c_i64, ctypes.c_float,
                                             ctypes.c_float, _vp, _c_sz, _vp]),
     "deig_gemm_skinny_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    "deig_procrustes_avg_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp, _c_i64,
+                                               ctypes.POINTER(ctypes.c_float), ctypes.c_int, _fp,
+                                               _c_i64, _fp, _fp, _vp, _c_sz, _vp]),
+    "deig_procrustes_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
+    "deig_subspace_dist_f32": (ctypes.c_int, [_fp, _c_i64, _fp, _c_i64, _c_i64, ctypes.c_int, _fp,
+                                              _vp, _c_sz, _vp]),
+    "deig_subspace_dist_workspace": (_c_sz, [_c_i64, ctypes.c_int]),
 }
 
 _lock = threading.Lock()

@@ -1647,6 +1647,27 @@ int deig_projavg_topk_f32(const float* Wt, int64_t d, int64_t mk, int64_t ldw, f
                               evals, sweeps_out, resid_out, nullptr, ws, ws_bytes, stream);
 }
 
+size_t deig_procrustes_workspace(int64_t d, int64_t mk, int k) {
+  return procrustes_workspace_bytes(d, mk, k);
+}
+
+int deig_procrustes_avg_f32(const float* Wt, int64_t d, int64_t mk, int64_t ldw, int k,
+                            const float* Vref, int64_t ldref, const float* weights, int iters,
+                            float* V, int64_t ldv, float* Z, float* cosines, void* ws,
+                            size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return procrustes_launch(Wt, d, mk, ldw, k, Vref, ldref, weights, iters, V, ldv, Z, cosines, ws,
+                           ws_bytes, (hipStream_t)stream);
+}
+
+size_t deig_subspace_dist_workspace(int64_t d, int k) { return subspace_dist_workspace_bytes(d, k); }
+
+int deig_subspace_dist_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t d, int k,
+                           float* out, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return subspace_dist_launch(A, lda, B, ldb, d, k, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int deig_sym_power_f32(const float* S, int64_t d, int64_t lds, float* Q, int p, int64_t ldq,
                        float* Y, int64_t ldy, const float* cs, int steps, int algo, void* ws,
                        size_t ws_bytes, void* stream) {

@@ -232,4 +232,15 @@ size_t project_workspace_bytes(int64_t n, int64_t d, int k);
 int project_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const float* W, int k,
                    int64_t ldw, float* Y, int64_t ldy, void* ws, size_t ws_bytes, hipStream_t st);
 
+// Procrustes-aligned basis average and residual-form subspace distance (procrustes.hip).
+// Both validate their arguments (DEIG_EINVAL) before any GPU work; the workspace
+// queries return 0 for shapes the launches reject.
+size_t procrustes_workspace_bytes(int64_t d, int64_t mk, int k);
+int procrustes_launch(const float* Wt, int64_t d, int64_t mk, int64_t ldw, int k, const float* Vref,
+                      int64_t ldref, const float* weights, int iters, float* V, int64_t ldv,
+                      float* Z, float* cosines, void* ws, size_t ws_bytes, hipStream_t st);
+size_t subspace_dist_workspace_bytes(int64_t d, int k);
+int subspace_dist_launch(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t d, int k,
+                         float* out, void* ws, size_t ws_bytes, hipStream_t st);
+
 }  // namespace deig

@@ -11,7 +11,9 @@ projectors (:126-130).  Here:
 * exchange: ONE collective - an all-gather of the fp32 bases (k x d rows each,
   i.e. the column-major d x k bytes) over RCCL/xGMI into Wt = [V_1^T; ...; V_M^T];
 * server: the implicit projector-average top-k on ``server_rank`` (GPU 0),
-  warm-started from V_1; the d x d average is never formed.
+  warm-started from V_1; the d x d average is never formed.  With
+  ``aggregate="procrustes"`` the server is the Procrustes-aligned average instead
+  (``linalg.procrustes_average``: no eigensolve, columns follow V_1's).
 
 The collective layer only uses ``torch.distributed`` with tensors on the rank's
 device, so it runs on ``gloo`` with CPU tensors too (multi-process tests); the
@@ -29,6 +31,9 @@ from . import linalg
 
 __all__ = ["shard_ranges", "rank_shards", "EstimatorResult", "DistributedEigenspaceEstimator",
            "gather_bases"]
+
+
+AGGREGATES = ("projector", "procrustes")
 
 
 def shard_ranges(n_rows: int, batches_number: int):
@@ -76,6 +81,7 @@ class EstimatorResult:
     worker_evals: list             # this rank's workers' eigenvalues
     sweeps_worker: list
     sweeps_server: int
+    cosines: torch.Tensor | None = None  # aggregate="procrustes": (m, k) cosines basis i / V_1
 
 
 def _batch_accepts(solver_kw: dict) -> bool:
@@ -95,7 +101,12 @@ def _gpu_worker(x: torch.Tensor, k: int, **kw):
 class DistributedEigenspaceEstimator:
     def __init__(self, k: int, workers_per_rank: int = 1, server_rank: int = 0, group=None,
                  worker_fn=None, solver_kw=None, concurrent_workers: bool = False,
-                 batched_workers: bool = True):
+                 batched_workers: bool = True, aggregate: str = "projector"):
+        if aggregate not in AGGREGATES:
+            raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+        # "projector" (default, the reference's server): top-k of the projector average;
+        # "procrustes": Procrustes-aligned average of the bases, reference V_1.
+        self.aggregator = aggregate
         self.k = int(k)
         self.wpr = int(workers_per_rank)
         # concurrent_workers (default GPU worker, W > 1): covariances back to back on
@@ -188,6 +199,9 @@ class DistributedEigenspaceEstimator:
         Wt = gather_bases(Wt_local, self.group)
         m = world * self.wpr
         if rank == self.server_rank:
+            if self.aggregator == "procrustes":
+                pr = linalg.procrustes_average(Wt, self.k)
+                return EstimatorResult(None, pr.V, Wt, evs, sw, 0, cosines=pr.cosines)
             r = self.server(Wt, m)
             return EstimatorResult(r.evals, r.V, Wt, evs, sw, r.sweeps)
         return EstimatorResult(None, None, Wt, evs, sw, 0)

@@ -24,6 +24,7 @@ __all__ = [
     "sigma_hat", "topk_eigh", "topk_eigh_batch", "projavg_topk", "oja_step", "default_subspace",
     "EigResult", "require_device_tensor", "project", "stack_bases", "gemm_skinny",
     "oja_steps", "oja_check", "sym_apply", "sym_power", "sigma_hat_u8", "sigma_hat_shift",
+    "procrustes_average", "subspace_distance", "projector_distance", "ProcrustesResult",
 ]
 
 DEFAULT_TOL = 1e-6
@@ -502,6 +503,125 @@ def projavg_topk(Wt: torch.Tensor, k: int, scale: float, *, p: int | None = None
     if dp != d:
         res.V = res.V[:d].t().contiguous().t()
     return res
+
+
+# ---------------------------------------------------------------- Procrustes average
+@dataclass
+class ProcrustesResult:
+    """Procrustes-aligned average of a stack of bases (``procrustes_average``)."""
+
+    V: torch.Tensor        # (d, k) float32, column-major; columns follow the reference basis
+    cosines: torch.Tensor  # (m, k) cosines of the principal angles basis i / reference, descending
+    Z: torch.Tensor        # (m, k, k) the alignment rotations Z_i (last pass)
+
+
+def _colmajor_basis(t, d: int, k: int, dp: int, device, name: str) -> torch.Tensor:
+    """(d, k) basis as a column-major float32 tensor of dp >= d rows (zero padded)."""
+    t = require_device_tensor(t, name)
+    if t.dim() != 2 or tuple(t.shape) != (d, k):
+        raise ValueError(f"{name} must have shape ({d}, {k}), got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} must live on {device}")
+    out = torch.zeros((k, dp), dtype=torch.float32, device=device)
+    out[:, :d] = t.t()
+    return out.t()
+
+
+def procrustes_average(Wt: torch.Tensor, k: int, *, ref=None, weights=None,
+                       iters: int = 1) -> ProcrustesResult:
+    """V = orth(sum_i w_i V_i Z_i) with Z_i the orthogonal Procrustes rotation of V_i onto
+    the reference basis (include/deig.h deig_procrustes_avg_f32): the one-pass
+    aggregator of Charisopoulos, Benson and Damle.  No eigensolve, and the columns of V
+    follow the reference's columns (``projavg_topk`` fixes only the span).
+
+    Wt = stack_bases(...) is (m k) x d row-major.  ref: None (the first basis of the
+    stack), an integer index into the stack, or a (d, k) tensor.  weights: m non-negative
+    numbers, not all zero (None: equal).  iters (1..8): pass t > 1 aligns to the result
+    of pass t - 1.  k <= 128.
+    """
+    Wt = require_device_tensor(Wt, "procrustes_average")
+    if Wt.dim() != 2:
+        raise ValueError("Wt must be 2-D ((m k) x d)")
+    mk, d = Wt.shape
+    k = int(k)
+    if not 1 <= k <= d:
+        raise ValueError(f"k={k} out of range [1, {d}]")
+    if k > MAX_P:
+        raise ValueError(f"procrustes_average takes k <= {MAX_P}; use projavg_topk above")
+    if mk < k or mk % k:
+        raise ValueError(f"Wt has {mk} rows, not a positive multiple of k={k}")
+    m = mk // k
+    dev = Wt.device
+    dp = _pad_dim(d)
+    if dp != d or Wt.stride(1) != 1 or Wt.stride(0) % 4 or Wt.data_ptr() % 16:
+        Wp = torch.zeros((mk, dp), dtype=torch.float32, device=dev)
+        Wp[:, :d] = Wt
+        Wt = Wp
+    rptr, ldref, rkeep = None, dp, None
+    if ref is not None:
+        if isinstance(ref, int):
+            if not 0 <= ref < m:
+                raise ValueError(f"ref index {ref} out of range [0, {m})")
+            # basis i of the stack: its k rows are the column-major d x k bytes
+            rkeep = Wt[ref * k:(ref + 1) * k]
+            ldref = Wt.stride(0)
+        else:
+            rkeep = _colmajor_basis(ref, d, k, dp, dev, "ref")
+            ldref = rkeep.stride(1)
+        rptr = rkeep.data_ptr()
+    wptr = None
+    if weights is not None:
+        wl = [float(x) for x in (weights.tolist() if hasattr(weights, "tolist") else weights)]
+        if len(wl) != m:
+            raise ValueError(f"weights must hold m = {m} numbers, got {len(wl)}")
+        wptr = (ctypes.c_float * m)(*wl)
+    V = _colmajor(dp, k, dev)
+    Z = torch.empty((m, k, k), dtype=torch.float32, device=dev)
+    cos = torch.empty((m, k), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.deig_procrustes_workspace(dp, mk, k)
+        ws = _workspace(dev, nbytes)
+        rc = L.deig_procrustes_avg_f32(Wt.data_ptr(), dp, mk, Wt.stride(0), k, rptr, ldref, wptr,
+                                       int(iters), V.data_ptr(), dp, Z.data_ptr(), cos.data_ptr(),
+                                       ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "deig_procrustes_avg_f32")
+    if dp != d:
+        V = V[:d].t().contiguous().t()
+    return ProcrustesResult(V=V, cosines=cos, Z=Z)
+
+
+def subspace_distance(A: torch.Tensor, B: torch.Tensor):
+    """(||sin Theta(A, B)||_F, ||sin Theta(A, B)||_2) of the spans of two orthonormal
+    (d, k) bases, computed on the device from the residual B - A (A^T B)
+    (include/deig.h deig_subspace_dist_f32): unlike the cosine forms it resolves
+    distances far below 1e-3 in float32.  Synchronises to return Python floats."""
+    A = require_device_tensor(A, "subspace_distance")
+    if A.dim() != 2:
+        raise ValueError("A must be a (d, k) basis")
+    d, k = A.shape
+    if not 1 <= k <= min(d, MAX_P):
+        raise ValueError(f"k={k} out of range [1, min(d, {MAX_P})]")
+    dev = A.device
+    dp = _pad_dim(d)
+    Ac = _colmajor_basis(A, d, k, dp, dev, "A")
+    Bc = _colmajor_basis(B, d, k, dp, dev, "B")
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.deig_subspace_dist_workspace(dp, k)
+        ws = _workspace(dev, nbytes)
+        rc = L.deig_subspace_dist_f32(Ac.data_ptr(), Ac.stride(1), Bc.data_ptr(), Bc.stride(1), dp,
+                                      k, out.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "deig_subspace_dist_f32")
+    fro, two = out.tolist()
+    return fro, two
+
+
+def projector_distance(A: torch.Tensor, B: torch.Tensor) -> float:
+    """||A A^T - B B^T||_F = sqrt(2) ||sin Theta(A, B)||_F of two orthonormal (d, k)
+    bases (``subspace_distance``)."""
+    return 2.0 ** 0.5 * subspace_distance(A, B)[0]
 
 
 # ---------------------------------------------------------------- Oja

@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import linalg
-from .estimator import comm_tensor, gather_bases
+from .estimator import AGGREGATES, comm_tensor, gather_bases
 
 __all__ = ["StreamingOja", "broadcast_basis"]
 
@@ -51,16 +51,30 @@ def _gpu_server(Wt: torch.Tensor, k: int, scale: float, q0: torch.Tensor) -> tor
     return linalg.projavg_topk(Wt, k, scale, q0=q0).V
 
 
+def _gpu_server_procrustes(Wt: torch.Tensor, k: int, scale: float, q0: torch.Tensor) -> torch.Tensor:
+    """Procrustes-aligned average with the server rank's current basis as the
+    reference: the aggregated columns stay where they were (no flips or rotations
+    inside the span between aggregations)."""
+    return linalg.procrustes_average(Wt, k, ref=q0).V
+
+
 class StreamingOja:
     """Per-rank Oja iterate with periodic projector-average aggregation.
 
     V0: (d, k) float32 initial basis on the rank's device (any strides; it is
     copied into a column-major buffer).  After ``aggregate()`` every rank holds
-    the server's basis, columns in ascending-eigenvalue order.
+    the server's basis, columns in ascending-eigenvalue order
+    (``aggregate="projector"``, the default) or, with ``aggregate="procrustes"``, the
+    Procrustes-aligned average whose columns follow the server rank's basis before
+    the aggregation.
     """
 
     def __init__(self, V0: torch.Tensor, eta: float, agg_every: int = 64, server_rank: int = 0,
-                 group=None, step_fn=None, server_fn=None, block_fn=None):
+                 group=None, step_fn=None, server_fn=None, block_fn=None,
+                 aggregate: str = "projector"):
+        if aggregate not in AGGREGATES:
+            raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+        self.aggregator = aggregate
         d, k = V0.shape
         self.k = int(k)
         self.V = torch.empty((k, d), dtype=torch.float32, device=V0.device).t()
@@ -70,7 +84,8 @@ class StreamingOja:
         self.server_rank = int(server_rank)
         self.group = group
         self.step_fn = step_fn or linalg.oja_step
-        self.server_fn = server_fn or _gpu_server
+        self.server_fn = server_fn or (_gpu_server_procrustes if aggregate == "procrustes"
+                                       else _gpu_server)
         self.block_fn = block_fn or linalg.oja_steps
         self.batches_seen = 0
         self.aggregations = 0

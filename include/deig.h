@@ -319,6 +319,46 @@ int deig_projavg_topk_ex(const float* Wt, int64_t d, int64_t mk, int64_t ldw, fl
                          const deig_solver_opts* opts, void* ws, size_t ws_bytes, void* stream);
 size_t deig_projavg_workspace_ex(int64_t d, int64_t mk, int k, int p, const deig_solver_opts* opts);
 
+/* Procrustes-aligned average of m bases (Charisopoulos, Benson, Damle: "Communication-
+ * efficient distributed eigenspace estimation"), the one-pass alternative to the
+ * projector-average server above (not in the reference; deig_projavg_topk stays the
+ * reference's aggregator):
+ *   V = orth( sum_i w_i V_i Z_i ),  Z_i = argmin_{Z in O(k)} ||V_i Z - R||_F = U W^T
+ *   for V_i^T R = U diag(c) W^T (c = cosines of the principal angles, descending).
+ * orth is the Loewdin (symmetric) orthonormalisation X (X^T X)^(-1/2), applied twice: the
+ * orthonormal basis closest to the average, so V keeps the COLUMNS of the reference R
+ * (column-wise eigenvector estimates), not only the span.  No eigensolve: two passes over
+ * Wt and m + 2 small k x k Jacobi SVDs per pass.
+ * Wt: the stack of deig_projavg_topk_f32, (mk) x d row-major (ldw), m = mk / k bases, read
+ * only.  Vref: the reference basis R, d x k column-major (ldref), NULL = V_1.  weights: m
+ * HOST floats >= 0, not all zero (only their ratios matter), NULL = equal; they are read
+ * before the call returns.  iters in 1..8: pass t > 1 aligns to pass t-1's V.  Outputs
+ * (device): V d x k column-major (ldv); Z (m x k x k row-major, Z_i of the last pass) and
+ * cosines (m x k, descending, last pass) may be NULL.
+ * Degenerate cosines: a singular value below 1e-5 c_max contributes no term to Z_i, which
+ * is then a partial isometry - the result stays finite (never NaN) and that worker
+ * contributes nothing along a direction of R it does not see.
+ * Requires 1 <= k <= 128 (above, the projector-average server remains the way), k <= d,
+ * mk a positive multiple of k, d % 4 == 0, ldw % 4 == 0, ldw >= d, 16-byte aligned Wt;
+ * anything else is DEIG_EINVAL before any GPU work.  Asynchronous on `stream`: no
+ * allocation, no synchronisation; repeated calls give bit-identical results. */
+int deig_procrustes_avg_f32(const float* Wt, int64_t d, int64_t mk, int64_t ldw, int k,
+                            const float* Vref, int64_t ldref, const float* weights, int iters,
+                            float* V, int64_t ldv, float* Z, float* cosines, void* ws,
+                            size_t ws_bytes, void* stream);
+size_t deig_procrustes_workspace(int64_t d, int64_t mk, int k);
+
+/* Distance of the spans of two orthonormal bases A, B (d x k column-major, lda / ldb):
+ * out[0] = ||sin Theta(A,B)||_F, out[1] = ||sin Theta(A,B)||_2 (device, 2 floats), from the
+ * residual form R = B - A (A^T B): out[0] = ||R||_F, out[1] = sqrt(lambda_max(R^T R)).
+ * Unlike the cosine forms (k - ||A^T B||_F^2, singular values of A^T B) it resolves
+ * distances far below 1e-3 in fp32.  ||P_A - P_B||_F = sqrt(2) out[0].
+ * Requires 1 <= k <= 128, k <= d, d % 4 == 0, lda % 4 == 0, 16-byte aligned A.
+ * Asynchronous on `stream`, no allocation, no synchronisation. */
+int deig_subspace_dist_f32(const float* A, int64_t lda, const float* B, int64_t ldb,
+                           int64_t d, int k, float* out, void* ws, size_t ws_bytes, void* stream);
+size_t deig_subspace_dist_workspace(int64_t d, int k);
+
 /* One mini-batch Oja step (online variant, BASELINE.json config 4; not in the
  * reference - parity unpinned):  V <- orth(V + eta/b * Xb^T (Xb V)).
  * Xb is b x d row-major (ldx), V is d x k column-major (ldv), updated in place.
