@@ -42,7 +42,7 @@ def _stale() -> bool:
 
 
 def build_library(force: bool = False, verbose: bool = True, defines=(), out: str | None = None) -> str:
-    """Build libdeig.so (or, with ``defines`` such as ``-DDEIG_AB_SYRK_VARIANT=22``, an
+    """Build libdeig.so (or, with ``defines`` such as ``-DDEIG_AB_SYRK_PACE=96``, an
     A/B variant into ``out`` - measurement tooling only; the shipped library reads
     no environment and has no knobs)."""
     lib = out or LIB

@@ -1163,9 +1163,7 @@ int solve_batch(int W, const Operator* ops, int64_t d, int k, int p, int max_swe
   // results are too (bit for bit).
   // (d >= 2048: below that the per-launch cost outweighs the overlap - config-1 gray
   // shards, d = 1024, measured 8 % slower with two groups)
-#if defined(DEIG_AB_BATCH_ONE_GROUP)
-  constexpr int kGroups = 1;
-#elif defined(DEIG_AB_BATCH_GROUPS)
+#ifdef DEIG_AB_BATCH_GROUPS
   constexpr int kGroups = DEIG_AB_BATCH_GROUPS;
 #else
   constexpr int kGroups = 2;

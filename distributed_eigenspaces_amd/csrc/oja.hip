@@ -250,17 +250,7 @@ __global__ __launch_bounds__(256) void trsm_img_kernel(const float* __restrict__
   }
 }
 
-// Measurement builds only (tools/ab.py build; the shipped library is variant 0):
-// -DDEIG_AB_OJA_VARIANT=N knocks parts out of the NN (N % 8) / TN ((N / 8) % 8)
-// passes - 1: no X loads, 2: no operand-image loads, 4: no MFMAs - and picks the
-// prefetch depth ((N / 64) % 4: 4, 2, 6, 8 k-steps); (N / 256) % 2 = 1: the TN
-// pass without its XCD-aware block order.
-#ifdef DEIG_AB_OJA_VARIANT
-constexpr int kOjaAB = DEIG_AB_OJA_VARIANT;
-#else
-constexpr int kOjaAB = 0;
-#endif
-constexpr int kOjaPF = ((kOjaAB / 64) % 4) == 0 ? 4 : ((kOjaAB / 64) % 4) == 1 ? 2 : ((kOjaAB / 64) % 4) == 2 ? 6 : 8;
+constexpr int kOjaPF = 4;  // prefetch depth of the NN / TN passes (k-steps)
 
 // NN: T = Xb V (b x kp), written as the TN pass's B-operand image (img_kernel's
 // layout; an 8-row group never straddles two blocks).  One 512-thread block per 16 rows of Xb,
@@ -270,7 +260,7 @@ constexpr int kOjaPF = ((kOjaAB / 64) % 4) == 0 ? 4 : ((kOjaAB / 64) % 4) == 1 ?
 // loads; the 16 rows x 128 B of a wave-instruction pair are whole lines), split to
 // hi / lo in registers; B from the V image (img_kernel), L2-resident.  Loads run
 // PF k-steps ahead of the MFMAs (register ring).
-template <int NB, int KO = kOjaAB % 8>
+template <int NB>
 __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X, int64_t ldx, int64_t b,
                                                      int d, int nks, const u32x4* __restrict__ vimg,
                                                      u32x4* __restrict__ timg) {
@@ -296,22 +286,12 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X
   u32x4 bh[PF][NB], bl[PF][NB];
   auto load = [&](int ks, int slot) {
     const int k = 32 * ks + 8 * (lane >> 4);
-    if constexpr (KO & 1) {
-      xa[slot] = f32x4{(float)k, 1.f, 2.f, 3.f};
-      xb[slot] = f32x4{(float)ks, 1.f, 2.f, 3.f};
-    } else {
-      xa[slot] = *reinterpret_cast<const f32x4*>(xr + min(k, d - 4));
-      xb[slot] = *reinterpret_cast<const f32x4*>(xr + min(k + 4, d - 4));
-    }
+    xa[slot] = *reinterpret_cast<const f32x4*>(xr + min(k, d - 4));
+    xb[slot] = *reinterpret_cast<const f32x4*>(xr + min(k + 4, d - 4));
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-      if constexpr (KO & 2) {
-        bh[slot][nb] = u32x4{(unsigned)ks, 1u, 2u, (unsigned)lane};
-        bl[slot][nb] = u32x4{(unsigned)k, 1u, 2u, (unsigned)lane};
-      } else {
-        bh[slot][nb] = vimg[img_index(ks, nb, 0, lane, NB)];
-        bl[slot][nb] = vimg[img_index(ks, nb, 1, lane, NB)];
-      }
+      bh[slot][nb] = vimg[img_index(ks, nb, 0, lane, NB)];
+      bl[slot][nb] = vimg[img_index(ks, nb, 1, lane, NB)];
     }
   };
   auto step = [&](int u) {
@@ -319,17 +299,11 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X
     split8(xa[u], xb[u], ahi, alo);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-      if constexpr (KO & 4) {  // keep the operands live without the MFMAs
-        const u32x4 a = __builtin_bit_cast(u32x4, ahi) ^ __builtin_bit_cast(u32x4, alo);
-        const u32x4 q = a ^ bh[u][nb] ^ bl[u][nb];
-        acc[nb] += __builtin_bit_cast(f32x4, q & u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u});
-      } else {
-        const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
-        const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
-        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc[nb], 0, 0, 0);
-        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc[nb], 0, 0, 0);
-        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc[nb], 0, 0, 0);
-      }
+      const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
+      const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc[nb], 0, 0, 0);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc[nb], 0, 0, 0);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc[nb], 0, 0, 0);
     }
   };
 #pragma unroll
@@ -389,7 +363,7 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X
 // them through its own LDS region ([feature][row], TS floats a row); B is the T
 // image (img_kernel).  An 8-feature group of the V image never straddles two
 // blocks (16 | 32), so each block writes its own image entries.
-template <int NB, int KO = (kOjaAB / 8) % 8>
+template <int NB>
 __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X, int64_t ldx, int64_t b,
                                                      int d, int nkr, const u32x4* __restrict__ timg,
                                                      float c, float* __restrict__ V,
@@ -403,7 +377,7 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // XCD-aware: the two blocks of a 32-feature (128-B) row segment run on one XCD
   // and share its L2 line (round-robin dispatch would split every pair over two)
-  const int f0 = ((kOjaAB / 256) % 2 ? (int)blockIdx.x : xcd_logical(blockIdx.x, gridDim.x)) * 16;
+  const int f0 = xcd_logical(blockIdx.x, gridDim.x) * 16;
   const int fl = 4 * (lane & 3);  // this lane's 4 features (load mapping)
   // unpredicated loads (see oja_nn_kernel): features >= d and rows >= b read clamped
   // in-range addresses; their products are dropped (f >= d) or meet zero T rows
@@ -422,22 +396,12 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X
   u32x4 bh[PF][NB], bl[PF][NB];
   auto load = [&](int ks, int slot) {
     const int64_t r = 32 * (int64_t)ks + (lane >> 2);
-    if constexpr (KO & 1) {
-      xa[slot] = f32x4{(float)r, 1.f, 2.f, 3.f};
-      xb[slot] = f32x4{(float)ks, 1.f, 2.f, 3.f};
-    } else {
-      xa[slot] = *reinterpret_cast<const f32x4*>(xb_ + min(r, b - 1) * ldx);
-      xb[slot] = *reinterpret_cast<const f32x4*>(xb_ + min(r + 16, b - 1) * ldx);
-    }
+    xa[slot] = *reinterpret_cast<const f32x4*>(xb_ + min(r, b - 1) * ldx);
+    xb[slot] = *reinterpret_cast<const f32x4*>(xb_ + min(r + 16, b - 1) * ldx);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-      if constexpr (KO & 2) {
-        bh[slot][nb] = u32x4{(unsigned)ks, 1u, 2u, (unsigned)lane};
-        bl[slot][nb] = u32x4{(unsigned)r, 1u, 2u, (unsigned)lane};
-      } else {
-        bh[slot][nb] = timg[img_index(ks, nb, 0, lane, NB)];
-        bl[slot][nb] = timg[img_index(ks, nb, 1, lane, NB)];
-      }
+      bh[slot][nb] = timg[img_index(ks, nb, 0, lane, NB)];
+      bl[slot][nb] = timg[img_index(ks, nb, 1, lane, NB)];
     }
   };
   const int rr = lane >> 2;
@@ -453,17 +417,11 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X
     split8(a0, a1, ahi, alo);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-      if constexpr (KO & 4) {  // keep the operands live without the MFMAs
-        const u32x4 a = __builtin_bit_cast(u32x4, ahi) ^ __builtin_bit_cast(u32x4, alo);
-        const u32x4 q = a ^ bh[u][nb] ^ bl[u][nb];
-        acc[nb] += __builtin_bit_cast(f32x4, q & u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u});
-      } else {
-        const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
-        const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
-        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc[nb], 0, 0, 0);
-        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc[nb], 0, 0, 0);
-        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc[nb], 0, 0, 0);
-      }
+      const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
+      const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc[nb], 0, 0, 0);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc[nb], 0, 0, 0);
+      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc[nb], 0, 0, 0);
     }
   };
 #pragma unroll
@@ -886,7 +844,6 @@ __global__ __launch_bounds__(512) void oja_blk_kernel(OjaBlk a) {
     }
     OB_STAMP(9, t == 0);
   }
-#ifndef DEIG_AB_OJA_COOP
   // The hand-off counters are left at zero for the next launch on this workspace
   // (no memset and its kernel boundary between runs): every block drains its own
   // counter atomics (vmcnt(0): performed, not just issued), then counts itself out;
@@ -902,7 +859,6 @@ __global__ __launch_bounds__(512) void oja_blk_kernel(OjaBlk a) {
       __hip_atomic_store(ce, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-#endif
 }
 
 struct OjaWs {
@@ -1032,7 +988,6 @@ bool oja_blk_fits() {
 
 template <int NB>
 hipError_t launch_oja_blk(int nks, const OjaBlk& a, hipStream_t st) {
-#ifndef DEIG_AB_OJA_COOP
   switch (nks) {
 #define DEIG_OJA_NKS(x)                                                                         \
   case x:                                                                                       \
@@ -1044,22 +999,6 @@ hipError_t launch_oja_blk(int nks, const OjaBlk& a, hipStream_t st) {
     default:
       return hipErrorInvalidValue;
   }
-#else
-  const void* fn = nullptr;
-  switch (nks) {
-#define DEIG_OJA_NKS(x) \
-  case x:               \
-    fn = reinterpret_cast<const void*>(&oja_blk_kernel<NB, x>); \
-    break;
-    DEIG_OJA_NKS(1) DEIG_OJA_NKS(2) DEIG_OJA_NKS(3) DEIG_OJA_NKS(4) DEIG_OJA_NKS(5) DEIG_OJA_NKS(6)
-#undef DEIG_OJA_NKS
-    default:
-      return hipErrorInvalidValue;
-  }
-  OjaBlk arg = a;
-  void* args[] = {&arg};
-  return hipLaunchCooperativeKernel(fn, dim3(OB_G), dim3(512), args, 0, st);
-#endif
 }
 
 int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
@@ -1105,12 +1044,8 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
   for (int64_t i0 = 0; i0 < nb;) {
     const int64_t i1 = std::min(nb, (i0 / orth_every + 1) * orth_every);
     if (blk) {
-#ifndef DEIG_AB_OJA_COOP
       // zeroed once per call: each launch leaves them at zero for the next
       if (i0 == 0) DEIG_HIP_CHECK(hipMemsetAsync(o.cnt, 0, OB_CNT_BYTES, st));
-#else
-      DEIG_HIP_CHECK(hipMemsetAsync(o.cnt, 0, OB_CNT_BYTES, st));
-#endif
       OjaBlk a;
       a.X = X + i0 * b * ldx;
       a.ldx = ldx;

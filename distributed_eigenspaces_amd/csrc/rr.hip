@@ -4,9 +4,10 @@
 // Per sweep the driver (capi.hip) keeps Z = [Q | Y] (d x 2p, row-major) with
 // Y = A Q, forms the Gram C = Z^T Z (skinny GEMM) and then:
 //
-//  rr_small_kernel (ONE workgroup, p <= 128, everything in LDS):
+//  rr_small2_kernel / rr_small2_batch_kernel (ONE workgroup per problem, p <= 128,
+//  everything in LDS; the body, rr_small2_body, documents the steps):
 //    M = Q^T Q, H = Q^T Y, G = Y^T Y taken from C;
-//    D = diag(M)^-1/2;  D M D = L L^T (Cholesky, pivots floored);
+//    D = diag(M)^-1/2;  D M D = L L^T (blocked Cholesky, pivots floored);
 //    H~ = L^-1 (D H D) L^-T;  H~ = U diag(lambda) U^T by parallel cyclic Jacobi
 //    (round-robin pairing, p/2 rotations per step, both sides applied from one
 //    read of the old matrix);  W = D L^-T U  (so the Ritz vectors Q W are
@@ -27,7 +28,6 @@
 namespace deig {
 namespace {
 
-constexpr int RT = 1024;
 constexpr int UR = 32;  // rows per rr_update block
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
@@ -59,38 +59,6 @@ __global__ __launch_bounds__(256) void rr_init_kernel(float* __restrict__ Z, int
   Z[r * 2 * p + j] = v;
 }
 
-// C = A B for p x p row-major matrices in LDS (p % 4 == 0, p <= 128): thread tid
-// owns the 4 x 4 block at (a0, b0) and returns it in acc (false: no block).  Per
-// 4-wide k step: 4 + 4 ds_read_b128 for 64 FMAs into independent accumulators
-// (the former one-output-per-thread loops were LDS-latency-bound chains).
-__device__ __forceinline__ bool lds_gemm4(const float* A, const float* B, int p, int tid,
-                                          float (&acc)[4][4], int& a0, int& b0) {
-  const int nt = p >> 2;
-  const bool act = tid < nt * nt;
-  const int tr = act ? tid / nt : 0;
-  a0 = 4 * tr;
-  b0 = 4 * (tid - tr * nt);
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
-  if (!act) return false;
-  for (int t = 0; t < p; t += 4) {
-    f32x4 ar[4], br[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ar[r] = *reinterpret_cast<const f32x4*>(A + (a0 + r) * p + t);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) br[u] = *reinterpret_cast<const f32x4*>(B + (t + u) * p + b0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(ar[r][u], br[u][c], acc[r][c]);
-  }
-  return true;
-}
-
 // Jacobi rotation (c, s) zeroing apq of [[app, apq], [apq, aqq]].  Hardware rcp /
 // sqrt / rsq (~1 ulp): the rotation only has to be orthogonal to rounding
 // (c = rsq(1 + t^2), s = t c), not the exact minimiser, and it sits on the
@@ -106,398 +74,55 @@ __device__ __forceinline__ void rr_rot_cs(float app, float aqq, float apq, float
   s = t * c;
 }
 
-template <int NT>
-__device__ __forceinline__ void rr_small_body(const float* __restrict__ Cg, int p,
-                                              float* __restrict__ Wout, float* __restrict__ lam_out,
-                                              float* __restrict__ cs_out, float* __restrict__ qs_out,
-                                              int* __restrict__ info, int max_jsweeps, float jrel) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int pp = p * p;
-  const int half = p >> 1;
-  float* X1 = sm;
-  float* X2 = sm + pp;
-  float* dsc = X2 + pp;   // p
-  float* lamv = dsc + p;  // p
-  float* gd = lamv + p;   // p
-  // p/2 rotations {cos, sin, row a, row b} (16-byte aligned: p % 16 == 0)
-  f32x4* rotp = reinterpret_cast<f32x4*>(gd + p);
-  int* rank = reinterpret_cast<int*>(rotp + half);  // p
-  float* nq = reinterpret_cast<float*>(rank + p);   // p: ||Q w_j||^2
-  float* red = nq + p;                              // NT/64 + 2
-  int* nrot = reinterpret_cast<int*>(red + NT / 64 + 2);
-  const int tid = threadIdx.x;
-  const int ldc = 2 * p;
-  const float* Mg = Cg;
-  const float* Hg = Cg + p;
-  const float* Gg = Cg + (int64_t)p * ldc + p;
-  // Phase clock (100 MHz realtime counter) into info[4..8] for DEIG_DEBUG.
-  const uint64_t t0 = wall_clock64();
-  auto stamp = [&](int slot) {
-    if (tid == 0) info[slot] = (int)(wall_clock64() - t0);
-  };
-
-  // ---- 0. D = diag(M)^-1/2;  X1 = D M D
-  for (int a = tid; a < p; a += NT) {
-    const float m = Mg[a * ldc + a];
-    dsc[a] = (m > 0.f && isfinite(m)) ? rsqrtf(m) : 1.0f;
-  }
-  if (tid == 0) {
-    info[0] = 0;
-    info[1] = 0;
-    info[2] = 0;
-    info[3] = 0;  // 1 once the Jacobi iteration has converged (not stopped by the cap)
-  }
-  __syncthreads();
-  for (int idx = tid; idx < pp; idx += NT) {
-    const int a = idx / p, b = idx - a * p;
-    X1[idx] = Mg[a * ldc + b] * dsc[a] * dsc[b];
-  }
-  __syncthreads();
-
-  // Thread groups for the triangular steps: eight consecutive lanes per row
-  // (or column) split every dot product, reduced with three xor-shuffles.
-  const int grp = tid >> 3, part = tid & 7;
-  auto sum8 = [](float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-  };
-
-  // ---- 1. Cholesky  D M D = L L^T  (left-looking, lower, in place in X1), pivots
-  //         floored.  Step j: group g finishes row i = j + g of column j from the
-  //         finished columns t < j - both dots split over its 8 lanes - and
-  //         recomputes the pivot itself, so one barrier per column.  The pivots
-  //         go to gd[] (X1's diagonal still holds D M D's, read by every group)
-  //         and onto the diagonal after the loop.
-  constexpr int NG = NT / 8;  // lane groups
-  for (int j = 0; j < p; ++j) {
-    for (int i = j + grp; i < p; i += NG) {
-      float sd = 0.f, so = 0.f;
-      for (int t = part; t < j; t += 8) {
-        const float ljt = X1[j * p + t];
-        sd = fmaf(ljt, ljt, sd);
-        so = fmaf(X1[i * p + t], ljt, so);
-      }
-      sd = sum8(sd);
-      so = sum8(so);
-      float v = X1[j * p + j] - sd;
-      // A pivot below 1e-6 (the column's part independent of the earlier ones is
-      // < 1e-3 of its norm: numerically dependent) decouples the column: unit
-      // pivot, zero sub-diagonal.  Its orthogonalised vector is then the tiny
-      // Gram-Schmidt residual (Ritz value ~0, renormalised in rr_update by qs),
-      // and L^-1 stays bounded - dividing the sub-diagonal by a floored pivot
-      // grew L^-1 geometrically over consecutive dependent columns (r02: inf).
-      const bool floored = !(v > 1e-6f);
-      const float ljj = floored ? 1.0f : sqrtf(v);
-      if (part == 0) {
-        if (i == j) {
-          gd[j] = ljj;
-          if (floored) info[0] += 1;
-        } else {
-          X1[i * p + j] = floored ? 0.f : (X1[i * p + j] - so) / ljj;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  for (int a = tid; a < p; a += NT) X1[a * p + a] = gd[a];
-  for (int idx = tid; idx < pp; idx += NT) X2[idx] = 0.f;
-  __syncthreads();
-  stamp(4);
-
-  // ---- 2. L^-1 (lower) into X2, row by row; group c owns column c of row i,
-  //         its dot over t in [c, i) split over the group's 8 lanes.
-  for (int i = 0; i < p; ++i) {
-    for (int c = grp; c <= i; c += NG) {
-      float sacc = 0.f;
-      for (int t = c + part; t < i; t += 8) sacc = fmaf(X1[i * p + t], X2[t * p + c], sacc);
-      sacc = sum8(sacc);
-      if (part == 0) X2[i * p + c] = ((c == i ? 1.0f : 0.0f) - sacc) / X1[i * p + i];
-    }
-    __syncthreads();
-  }
-  stamp(5);
-
-  // ---- 3. X1 = D H D ; 4. T = L^-1 X1, stored transposed (X1 = T^T = X1^T L^-T);
-  //         5. X1 = L^-1 X1 = L^-1 H^T L^-T (symmetrised below: the same H~).
-  //         Register-blocked 4 x 4 products (lds_gemm4).
-  for (int idx = tid; idx < pp; idx += NT) {
-    const int a = idx / p, b = idx - a * p;
-    X1[idx] = Hg[a * ldc + b] * dsc[a] * dsc[b];
-  }
-  __syncthreads();
-  {
-    float acc[4][4];
-    int a0, b0;
-    bool act = lds_gemm4(X2, X1, p, tid, acc, a0, b0);
-    __syncthreads();
-    if (act)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) X1[(b0 + c) * p + a0 + r] = acc[r][c];
-    __syncthreads();
-    act = lds_gemm4(X2, X1, p, tid, acc, a0, b0);
-    __syncthreads();
-    if (act)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) X1[(a0 + r) * p + b0 + c] = acc[r][c];
-    __syncthreads();
-  }
-  // symmetrise H~ and turn X2 = L^-1 into the eigenvector accumulator V0 = L^-T:
-  // every Jacobi rotation right-multiplies it, so at the end X2 = L^-T U.
-  for (int idx = tid; idx < pp; idx += NT) {
-    const int a = idx / p, b = idx - a * p;
-    if (a < b) {
-      const float v = 0.5f * (X1[a * p + b] + X1[b * p + a]);
-      X1[a * p + b] = v;
-      X1[b * p + a] = v;
-      const float l = X2[b * p + a];  // L^-1 is lower: (b, a) holds the value
-      X2[a * p + b] = l;
-      X2[b * p + a] = 0.f;
-    }
-  }
-  __syncthreads();
-
-  stamp(6);
-  // ---- 6. parallel cyclic Jacobi on X1 (round-robin pairs; each thread owns a 2x2
-  //         block of the rotated matrix, updated in place from one read).
-  // nrot[0]: rotations in this sweep; nrot[1], nrot[2]: per-step counters used on
-  // alternating steps, so a counter is only reset after every thread has read it.
-  if (tid == 0) {
-    nrot[1] = 0;
-    nrot[2] = 0;
-  }
-  // idx = tid + u NT  ->  (idx / half, idx % half), stepped without divisions
-  const int tr0 = tid / half, tc0 = tid - tr0 * half;
-  const int dq = NT / half, dr = NT - dq * half;
-  for (int sw = 0; sw < max_jsweeps; ++sw) {
-    if (tid == 0) nrot[0] = 0;
-    // scale for the absolute rotation threshold
-    float dmax = 0.f;
-    for (int a = tid; a < p; a += NT) dmax = fmaxf(dmax, fabsf(X1[a * p + a]));
-    for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = dmax;
-    __syncthreads();
-    float amax = 0.f;
-    for (int i = 0; i < NT / 64; ++i) amax = fmaxf(amax, red[i]);
-    const float abs_thr = 1e-9f * amax;
-    // Convergence pre-check (one pass, one barrier): if no pair passes the
-    // rotation test now, the first step rotates nothing, the matrix stays as it
-    // is and so does every later step - the sweep would be a no-op.  Saves the
-    // all-identity sweep that used to end every solve (p - 1 steps, 2 barriers each).
-    {
-      int need = 0;
-      for (int idx = tid; idx < p * p && !need; idx += NT) {
-        const int a = idx / p, b = idx - a * p;
-        if (b < a) {
-          const float apq = X1[a * p + b];
-          need = fabsf(apq) > abs_thr &&
-                 fabsf(apq) > jrel * sqrtf(fabsf(X1[a * p + a] * X1[b * p + b]));
-        }
-      }
-      need = __syncthreads_or(need);
-      if (!need) {
-        if (tid == 0) info[3] = 1;
-        break;
-      }
-    }
-    for (int st = 0; st < p - 1; ++st) {
-      const int ci = 1 + (st & 1);
-      if (tid < half) {
-        int a, b;
-        if (tid == 0) {
-          a = p - 1;
-          b = st;
-        } else {
-          a = (st + tid) % (p - 1);
-          b = (st - tid + (p - 1)) % (p - 1);
-        }
-        const float app = X1[a * p + a], aqq = X1[b * p + b], apq = X1[a * p + b];
-        float c = 1.f, s = 0.f;
-        if (fabsf(apq) > abs_thr &&
-            fabsf(apq) > jrel * __builtin_amdgcn_sqrtf(fabsf(app * aqq))) {
-          rr_rot_cs(app, aqq, apq, c, s);
-          atomicAdd(nrot + ci, 1);
-        }
-        rotp[tid] = f32x4{c, s, __int_as_float(a), __int_as_float(b)};
-      }
-      __syncthreads();
-      const int step_rot = nrot[ci];
-      if (step_rot != 0) {  // wave-uniform: identity steps apply nothing
-        int tr = tr0, tc = tc0;
-        for (int idx = tid; idx < half * half; idx += NT) {
-          const f32x4 qr = rotp[tr], qc = rotp[tc];
-          const int ar = __float_as_int(qr[2]), br = __float_as_int(qr[3]);
-          const int ac = __float_as_int(qc[2]), bc = __float_as_int(qc[3]);
-          const float cr = qr[0], sr = qr[1], cc = qc[0], sc = qc[1];
-          const float x = X1[ar * p + ac], y = X1[ar * p + bc];
-          const float z = X1[br * p + ac], w = X1[br * p + bc];
-          // columns: col_a' = c col_a - s col_b ; col_b' = s col_a + c col_b
-          const float x1 = cc * x - sc * y, y1 = sc * x + cc * y;
-          const float z1 = cc * z - sc * w, w1 = sc * z + cc * w;
-          // rows
-          X1[ar * p + ac] = cr * x1 - sr * z1;
-          X1[br * p + ac] = sr * x1 + cr * z1;
-          X1[ar * p + bc] = cr * y1 - sr * w1;
-          X1[br * p + bc] = sr * y1 + cr * w1;
-          tr += dq;
-          tc += dr;
-          if (tc >= half) {
-            tc -= half;
-            ++tr;
-          }
-        }
-        tr = tr0;
-        tc = tc0;
-        for (int idx = tid; idx < p * half; idx += NT) {
-          const int r = tr, t = tc;
-          tr += dq;
-          tc += dr;
-          if (tc >= half) {
-            tc -= half;
-            ++tr;
-          }
-          const f32x4 qt = rotp[t];
-          const int a = __float_as_int(qt[2]), b = __float_as_int(qt[3]);
-          const float c = qt[0], s = qt[1];
-          const float va = X2[r * p + a], vb = X2[r * p + b];
-          X2[r * p + a] = c * va - s * vb;
-          X2[r * p + b] = s * va + c * vb;
-        }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        nrot[0] += step_rot;
-        nrot[ci] = 0;
-      }
-    }
-    __syncthreads();
-    const int swrot = nrot[0];
-    if (tid == 0) {
-      info[1] = sw + 1;
-      info[2] += swrot;
-    }
-    __syncthreads();
-    if (swrot == 0) {
-      if (tid == 0) info[3] = 1;
-      break;
-    }
-  }
-
-  stamp(7);
-  // ---- 7. eigenvalues; W = D (L^-T U)  (row scaling, in place in X2)
-  for (int a = tid; a < p; a += NT) lamv[a] = X1[a * p + a];
-  __syncthreads();
-  for (int idx = tid; idx < pp; idx += NT) {
-    const int a = idx / p, b = idx - a * p;
-    X2[idx] *= dsc[a];
-    X1[idx] = Gg[a * ldc + b];
-  }
-  __syncthreads();
-  // ---- 8. g_j = w_j^T G w_j:  X1 = (G W) .* W, column sums below
-  {
-    float acc[4][4];
-    int a0, b0;
-    const bool act = lds_gemm4(X1, X2, p, tid, acc, a0, b0);
-    __syncthreads();
-    if (act)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          X1[(a0 + r) * p + b0 + c] = acc[r][c] * X2[(a0 + r) * p + b0 + c];
-    __syncthreads();
-  }
-  for (int j = tid; j < p; j += NT) {
-    float s = 0.f;
-    for (int a = 0; a < p; ++a) s += X1[a * p + j];
-    gd[j] = s;
-  }
-  __syncthreads();
-  // ---- 9. n_j = w_j^T M w_j = ||Q w_j||^2: 1 up to rounding when D M D was
-  //         factored exactly, but not for columns whose pivot was floored (a
-  //         numerically dependent Q): their Ritz vectors are renormalised by it,
-  //         or repeated floored RR steps compound their norms until they overflow.
-  for (int idx = tid; idx < pp; idx += NT) {
-    const int a = idx / p, b = idx - a * p;
-    X1[idx] = Mg[a * ldc + b];
-  }
-  __syncthreads();
-  {
-    float acc[4][4];
-    int a0, b0;
-    const bool act = lds_gemm4(X1, X2, p, tid, acc, a0, b0);
-    __syncthreads();
-    if (act)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          X1[(a0 + r) * p + b0 + c] = acc[r][c] * X2[(a0 + r) * p + b0 + c];
-    __syncthreads();
-  }
-  for (int j = tid; j < p; j += NT) {
-    float s = 0.f;
-    for (int a = 0; a < p; ++a) s += X1[a * p + j];
-    nq[j] = s;
-    const float lj = lamv[j];
-    int rk = 0;
-    for (int b = 0; b < p; ++b) {
-      const float lb = lamv[b];
-      rk += (lb > lj || (lb == lj && b < j)) ? 1 : 0;
-    }
-    rank[j] = rk;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float mx = 0.f;
-    for (int j = 0; j < p; ++j) mx = fmaxf(mx, gd[j]);
-    red[0] = mx;
-  }
-  __syncthreads();
-  const float gthr = red[0] * 1e-10f;
-  for (int j = tid; j < p; j += NT) {
-    const int rk = rank[j];
-    lam_out[rk] = lamv[j];
-    cs_out[rk] = (gd[j] > gthr && gd[j] > 0.f) ? rsqrtf(gd[j]) : 0.f;
-    qs_out[rk] = (nq[j] > 1e-30f && isfinite(nq[j])) ? rsqrtf(nq[j]) : 1.f;
-  }
-  for (int idx = tid; idx < pp; idx += NT) {
-    const int a = idx / p, j = idx - a * p;
-    Wout[a * p + rank[j]] = X2[idx];
-  }
-  stamp(8);
-}
-
-// ---------------------------------------------------------------- small solve v2
-// The same generalised Rayleigh-Ritz step as rr_small_body (same outputs, same
-// decisions), restructured for the barrier / LDS-instruction budget of ONE
-// workgroup (r04: rr_small_body spent ~1.4 us per Jacobi step at p = 80 - 2 barriers
-// and ~40 LDS instructions per thread - and 2 x p barriers in the column-by-column
-// Cholesky and L^-1):
-//  * Cholesky of D M D and L^-1 in 16-column blocks: each 16 x 16 diagonal block is
-//    factored and inverted by one wave in registers (readlane broadcasts, no
-//    barrier), panels / trailing updates / block products are LDS-tiled products -
-//    ~4 barriers per block instead of 32;
-//  * Jacobi on the LOWER triangle only (half the block updates; stored with row
-//    stride p + 1 so column-strided accesses spread over the banks) and the
-//    eigenvector accumulator V held in REGISTERS: the round-robin ordering is the
-//    circle method, so the logical columns a pair slot holds move one slot per step in
-//    a fixed pattern (a-players down, b-players up); a row of V is split over 4 lanes
-//    (p / 8 slots each) that pass 2 values per step to their neighbours by shuffles.
-// Numerically: the Cholesky is right-looking by blocks (rounding order differs from
-// rr_small_body), the pivot floor and every later decision are the same.
+// ---------------------------------------------------------------- small solve
+// rr_small2_body: the generalised Rayleigh-Ritz step of ONE workgroup on the 2p x 2p
+// Gram C = [Q | Y]^T [Q | Y] (M = Q^T Q, H = Q^T Y, G = Y^T Y), X1 and X2 two p x p
+// matrices in LDS (row stride p).  Outputs: W (p x p), lam, cs, qs with the columns
+// sorted by descending lambda; info[0] floored pivots, info[1] Jacobi sweeps, info[2]
+// rotations, info[3] 1 once the Jacobi iteration has converged (not stopped by the
+// cap), info[4..8] a phase clock (100 MHz realtime counter) for DEIG_DEBUG.
+//  0. D = diag(M)^-1/2, X1 = D M D.
+//  1. Cholesky D M D = L L^T, right-looking in 16-column blocks: each 16 x 16 diagonal
+//     block is factored and inverted by one wave in registers (chol16_wave: readlane
+//     broadcasts, no barrier); panels and trailing updates are LDS-tiled 4 x 4 products
+//     - ~4 barriers per block (r04: the column-by-column form took 2 x p barriers for
+//     the Cholesky and L^-1).
+//     Pivot floor: a pivot below 1e-6 (the column's part independent of the earlier
+//     ones is < 1e-3 of its norm: numerically dependent) decouples the column: unit
+//     pivot, zero sub-diagonal.  Its orthogonalised vector is then the tiny
+//     Gram-Schmidt residual (Ritz value ~0, renormalised in rr_update by qs), and L^-1
+//     stays bounded - dividing the sub-diagonal by a floored pivot grew L^-1
+//     geometrically over consecutive dependent columns (r02: inf).
+//  2. L^-1 (lower) into X2 by block rows.
+//  3. H~ = L^-1 (D H D) L^-T in X1 (two tiled products), symmetrised in step 4.
+//  4. H~ = U diag(lambda) U^T by parallel cyclic Jacobi on the FULL matrix: a sweep is
+//     p - 1 steps of p / 2 disjoint round-robin pairs (pair t of step st: a = (st + t)
+//     mod (p - 1), b = (st - t) mod (p - 1), pair 0: a = p - 1, b = st); wave 0 forms
+//     the step's rotations, then every thread applies them from both sides to its
+//     2 x 2 blocks of X1, each updated in place from one read: 2 barriers per step.  A
+//     pair rotates when |a_pq| exceeds both 1e-9 max|a_ii| and jrel sqrt|a_pp a_qq|; a
+//     step without rotations applies nothing, and a pre-check ends the iteration
+//     without running an all-identity sweep (p - 1 steps) when no pair passes the test.
+//     nrot[0]: rotations of the sweep; nrot[1], nrot[2]: the step's count, used on
+//     alternating steps so that one is only rewritten after every thread has read it.
+//     The eigenvector accumulator starts as V0 = L^-T and is right-multiplied by every
+//     rotation (at the end V = L^-T U); it is kept TRANSPOSED in X2 (V^T, which L^-1
+//     already is), so a column pair's rotation updates two contiguous rows.
+//  5. lambda = diag(X1); X2 transposed back; W = D V (so the Ritz vectors Q W are
+//     orthonormal even when Q is not).
+//  6. g_j = w_j^T G w_j = ||Y w_j||^2 and n_j = w_j^T M w_j = ||Q w_j||^2 as column
+//     sums of (G W) .* W and (M W) .* W.  n_j is 1 up to rounding when D M D was
+//     factored exactly, but not for columns whose pivot was floored (a numerically
+//     dependent Q): their Ritz vectors are renormalised by it (qs), or repeated floored
+//     RR steps compound their norms until they overflow.  cs_j = g_j^-1/2 (0 for
+//     g_j ~ 0: null directions of A).
 __device__ __forceinline__ float rdl(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
 // One wave: Cholesky of the 16 x 16 block at (o, o) of X1 (row stride p, already
-// updated by the earlier blocks), written back as L_JJ (lower; pivots floored as in
-// rr_small_body: v <= 1e-6 -> unit pivot, zero sub-diagonal); L_JJ^-1 written to the
+// updated by the earlier blocks), written back as L_JJ (lower; pivots floored, see
+// above: v <= 1e-6 -> unit pivot, zero sub-diagonal); L_JJ^-1 written to the
 // diagonal block of X2 (row-major, zero upper) and to LS (16 x 17, row-major padded).
 __device__ __forceinline__ void chol16_wave(float* X1, float* X2, float* LS, int* flo, int p, int o,
                                             int lane, int* info) {
@@ -770,8 +395,8 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
   }
   stamp(6);
 
-  // ---- 4. Jacobi (rr_small_body's: full storage, round-robin pairs, 2 barriers per
-  //         step; r04 A/B: every restructured step measured slower - V in registers
+  // ---- 4. Jacobi (full storage, round-robin pairs, 2 barriers per step; r04 A/B:
+  //         every restructured step measured slower - V in registers
   //         moved along the circle method, lower-triangle storage, rotations per wave
   //         by shuffles - their extra VALU / shuffle issue cost more than the LDS
   //         traffic they saved, profiles/r04d_rr_phases.log).
@@ -785,13 +410,7 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
       const float v = 0.5f * (X1[a * p + b] + X1[b * p + a]);
       X1[a * p + b] = v;
       X1[b * p + a] = v;
-#if defined(DEIG_AB_RR_JOLD) || defined(DEIG_AB_RR_VROW)
-      const float l = X2[b * p + a];
-      X2[a * p + b] = l;
-      X2[b * p + a] = 0.f;
-#else
       X2[a * p + b] = 0.f;
-#endif
     }
   }
   if (tid == 0) {
@@ -800,19 +419,13 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
   }
   __syncthreads();
   const int tr0 = tid / half, tc0 = tid - tr0 * half;
-#ifdef DEIG_AB_RR_JOLD
-  const int dq = NT / half, dr = NT - dq * half;
-#else
   const int cpt = NT / half;
-#ifndef DEIG_AB_RR_VROW
   // V^T items: (column pair t, quad q of its two rows), t-major so that a wave's lanes
   // walk contiguous quads of one row pair
   const int vnq = p >> 2;
   // (counted from the last thread: at small p the first waves carry the H~ update)
   const int vt0 = (NT - 1 - tid) / vnq, vq0 = (NT - 1 - tid) - vt0 * vnq;
   const int vdt = NT / vnq, vdq = NT - vdt * vnq;
-#endif
-#endif
   for (int sw = 0; sw < max_jsweeps; ++sw) {
     if (tid == 0) nrot[0] = 0;
     float dmax = 0.f;
@@ -844,25 +457,6 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
     int swsum = 0;  // wave 0: this sweep's rotations
     for (int st = 0; st < p - 1; ++st) {
       const int ci = 1 + (st & 1);
-#ifdef DEIG_AB_RR_JOLD
-      if (tid < half) {
-        int a, b;
-        if (tid == 0) {
-          a = p - 1;
-          b = st;
-        } else {
-          a = (st + tid) % (p - 1);
-          b = (st - tid + (p - 1)) % (p - 1);
-        }
-        const float app = X1[a * p + a], aqq = X1[b * p + b], apq = X1[a * p + b];
-        float c = 1.f, s = 0.f;
-        if (fabsf(apq) > abs_thr && fabsf(apq) > jrel * __builtin_amdgcn_sqrtf(fabsf(app * aqq))) {
-          rr_rot_cs(app, aqq, apq, c, s);
-          atomicAdd(nrot + ci, 1);
-        }
-        rotp[tid] = f32x4{c, s, __int_as_float(a), __int_as_float(b)};
-      }
-#else
       // the p / 2 <= 64 pairs of a step are one wave's lanes: the step's rotation count
       // is a ballot (64 LDS atomics on one address serialised ~0.2 us per step)
       if (wave == 0) {
@@ -883,50 +477,9 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
         if (tid == 0) nrot[ci] = cnt;
         swsum += cnt;
       }
-#endif
       __syncthreads();
       const int step_rot = nrot[ci];
       if (step_rot != 0) {
-#ifdef DEIG_AB_RR_JOLD
-        int tr = tr0, tc = tc0;
-        for (int idx = tid; idx < half * half; idx += NT) {
-          const f32x4 qr = rotp[tr], qc = rotp[tc];
-          const int ar = __float_as_int(qr[2]), br = __float_as_int(qr[3]);
-          const int ac = __float_as_int(qc[2]), bc = __float_as_int(qc[3]);
-          const float cr = qr[0], sr = qr[1], cc = qc[0], sc = qc[1];
-          const float x = X1[ar * p + ac], y = X1[ar * p + bc];
-          const float z = X1[br * p + ac], w = X1[br * p + bc];
-          const float x1 = cc * x - sc * y, y1 = sc * x + cc * y;
-          const float z1 = cc * z - sc * w, w1 = sc * z + cc * w;
-          X1[ar * p + ac] = cr * x1 - sr * z1;
-          X1[br * p + ac] = sr * x1 + cr * z1;
-          X1[ar * p + bc] = cr * y1 - sr * w1;
-          X1[br * p + bc] = sr * y1 + cr * w1;
-          tr += dq;
-          tc += dr;
-          if (tc >= half) {
-            tc -= half;
-            ++tr;
-          }
-        }
-        tr = tr0;
-        tc = tc0;
-        for (int idx = tid; idx < p * half; idx += NT) {
-          const int r = tr, t = tc;
-          tr += dq;
-          tc += dr;
-          if (tc >= half) {
-            tc -= half;
-            ++tr;
-          }
-          const f32x4 qt = rotp[t];
-          const int a = __float_as_int(qt[2]), b = __float_as_int(qt[3]);
-          const float c = qt[0], s = qt[1];
-          const float va = X2[r * p + a], vb = X2[r * p + b];
-          X2[r * p + a] = c * va - s * vb;
-          X2[r * p + b] = s * va + c * vb;
-        }
-#else
         // thread -> column pair tc0 and every cpt-th row pair (and V row): the column
         // pair's rotation record is read once per step instead of once per 2 x 2 block
         // and V item (the step is LDS-bound: at p = 128, 524 -> 360 KB per step)
@@ -947,15 +500,7 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
             X1[ar * p + bc] = cr * y1 - sr * w1;
             X1[br * p + bc] = sr * y1 + cr * w1;
           }
-#if defined(DEIG_AB_RR_VROW) && !defined(DEIG_AB_RR_NO_V)  // r05 layout (measurement builds)
-          for (int r = tr0; r < p; r += cpt) {
-            const float va = X2[r * p + ac], vb = X2[r * p + bc];
-            X2[r * p + ac] = cc * va - sc * vb;
-            X2[r * p + bc] = sc * va + cc * vb;
-          }
-#endif
         }
-#if !defined(DEIG_AB_RR_VROW) && !defined(DEIG_AB_RR_NO_V)  // NO_V: knock-out, wrong vectors
         for (int t = vt0, q = vq0; t < half;) {
           const f32x4 qc = rotp[t];
           const float cc = qc[0], sc = qc[1];
@@ -977,20 +522,10 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
             ++t;
           }
         }
-#endif
-#endif
       }
       __syncthreads();
-#ifdef DEIG_AB_RR_JOLD
-      if (tid == 0) {
-        nrot[0] += step_rot;
-        nrot[ci] = 0;
-      }
-#endif
     }
-#ifndef DEIG_AB_RR_JOLD
     if (tid == 0) nrot[0] = swsum;
-#endif
     __syncthreads();
     const int swrot = nrot[0];
     if (tid == 0) {
@@ -1007,7 +542,6 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
   stamp(7);
   // ---- 5. eigenvalues; W = D (L^-T U) in X2 (row scaling in place); X1 = scratch
   for (int a = tid; a < p; a += NT) lamv[a] = X1[a * p + a];
-#if !defined(DEIG_AB_RR_JOLD) && !defined(DEIG_AB_RR_VROW)
   for (int it = tid; it < nt4 * (nt4 + 1) / 2; it += NT) {  // V^T -> V by 4 x 4 blocks
     int ti, tj;
     tri_rc(it, ti, tj);
@@ -1023,7 +557,6 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
       *reinterpret_cast<f32x4*>(X2 + (4 * tj + r) * p + 4 * ti) = f32x4{A[0][r], A[1][r], A[2][r], A[3][r]};
     }
   }
-#endif
   __syncthreads();
   for (int idx = tid; idx < pp; idx += NT) X2[idx] *= dsc[idx / p];
   float* Wm = X2;   // W = D L^-T U
@@ -1107,17 +640,6 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
 }
 
 template <int NT>
-__global__ __launch_bounds__(NT) void rr_small_kernel(const float* __restrict__ Cg, int p,
-                                                      float* __restrict__ Wout,
-                                                      float* __restrict__ lam_out,
-                                                      float* __restrict__ cs_out,
-                                                      float* __restrict__ qs_out,
-                                                      int* __restrict__ info, int max_jsweeps,
-                                                      float jrel) {
-  rr_small_body<NT>(Cg, p, Wout, lam_out, cs_out, qs_out, info, max_jsweeps, jrel);
-}
-
-template <int NT>
 __global__ __launch_bounds__(NT) void rr_small2_kernel(const float* __restrict__ Cg, int p,
                                                        float* __restrict__ Wout,
                                                        float* __restrict__ lam_out,
@@ -1139,12 +661,6 @@ struct RRBatchArgs {
   int* info[kRRBatch];
   int max_jsweeps[kRRBatch];
 };
-
-template <int NT>
-__global__ __launch_bounds__(NT) void rr_small_batch_kernel(RRBatchArgs a, int p, float jrel) {
-  const int i = blockIdx.x;
-  rr_small_body<NT>(a.C[i], p, a.W[i], a.lam[i], a.cs[i], a.qs[i], a.info[i], a.max_jsweeps[i], jrel);
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void rr_small2_batch_kernel(RRBatchArgs a, int p, float jrel) {
@@ -1756,14 +1272,13 @@ __global__ __launch_bounds__(256) void rq_finish_kernel(const double* __restrict
   if (tid == 0 && rn[0] > 0.0) evals[j] = (float)(rq[0] / rn[0]);
 }
 
-size_t rr_small_shm(int p) {
-  return (size_t)(2 * p * p + 7 * p + RT / 64 + 20) * sizeof(float);
-}
-
 #ifdef DEIG_AB_RR_THREADS
 constexpr int RT2 = DEIG_AB_RR_THREADS;  // measurement builds
 #else
-constexpr int RT2 = 1024;  // rr_small2 (the Jacobi's per-step work wants every thread)
+// 1024 threads at every p: each Jacobi step is a chain of LDS round trips per thread, so
+// the most threads (shortest per-thread chain) win (r02 at p = 32: Jacobi 75 us with
+// 1024 threads, 89 with 256, 184 with 64 per RR).
+constexpr int RT2 = 1024;
 #endif
 size_t rr_small2_shm(int p) {
   return (size_t)(2 * p * p + 9 * p + 16 * 17 + 4 + 16 * (p + 4) + RT2 / 64 + 2 + 4) * sizeof(float);
@@ -1782,7 +1297,6 @@ int rr_init_launch(float* Z, int64_t d, int p, const float* Q0, int k0, int64_t 
 
 int rr_small_launch(const RRBuffers& b, int p, hipStream_t stream, int max_jsweeps, float jrel) {
   DEIG_REQUIRE(p >= 16 && p <= 128 && p % 16 == 0, "rr_small: p=%d out of range", p);
-#ifndef DEIG_AB_RR_V1
   static const hipError_t attr2 = hipFuncSetAttribute(
       (const void*)rr_small2_kernel<RT2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rr_small2_shm(128));
   DEIG_HIP_CHECK(attr2);
@@ -1790,35 +1304,15 @@ int rr_small_launch(const RRBuffers& b, int p, hipStream_t stream, int max_jswee
                      b.cs, b.qs, b.info, max_jsweeps, jrel);
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
-#endif
-  const size_t shm = rr_small_shm(p);
-  // once per process (C++11 thread-safe static initialisation)
-  static const hipError_t attr = hipFuncSetAttribute(
-      (const void*)rr_small_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-      (int)rr_small_shm(128));
-  DEIG_HIP_CHECK(attr);
-  // Workgroup size: 1024 threads at every p.  Each Jacobi step is a chain of LDS
-  // round trips per thread, so the most threads (shortest per-thread chain) win:
-  // measured r02 at p = 32, Jacobi 75 us (1024) vs 89 (256) vs 184 (64) per RR.
-  hipLaunchKernelGGL(rr_small_kernel<RT>, dim3(1), dim3(RT), shm, stream, b.C, p, b.W, b.lam, b.cs,
-                     b.qs, b.info, max_jsweeps, jrel);
-  DEIG_HIP_CHECK(hipGetLastError());
-  return DEIG_OK;
 }
 
 int rr_small_batch_launch(const RRBuffers* const* bs, const int* max_jsweeps, int n, int p,
                           hipStream_t stream, float jrel) {
   DEIG_REQUIRE(p >= 16 && p <= 128 && p % 16 == 0, "rr_small: p=%d out of range", p);
-#ifndef DEIG_AB_RR_V1
   static const hipError_t attr2 = hipFuncSetAttribute(
       (const void*)rr_small2_batch_kernel<RT2>, hipFuncAttributeMaxDynamicSharedMemorySize,
       (int)rr_small2_shm(128));
   DEIG_HIP_CHECK(attr2);
-#endif
-  static const hipError_t attr = hipFuncSetAttribute(
-      (const void*)rr_small_batch_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-      (int)rr_small_shm(128));
-  DEIG_HIP_CHECK(attr);
   for (int i0 = 0; i0 < n; i0 += kRRBatch) {
     const int m = std::min(kRRBatch, n - i0);
     RRBatchArgs a{};
@@ -1832,11 +1326,7 @@ int rr_small_batch_launch(const RRBuffers* const* bs, const int* max_jsweeps, in
       a.info[i] = b.info;
       a.max_jsweeps[i] = max_jsweeps[i0 + i];
     }
-#ifndef DEIG_AB_RR_V1
     hipLaunchKernelGGL(rr_small2_batch_kernel<RT2>, dim3(m), dim3(RT2), rr_small2_shm(p), stream, a, p, jrel);
-#else
-    hipLaunchKernelGGL(rr_small_batch_kernel<RT>, dim3(m), dim3(RT), rr_small_shm(p), stream, a, p, jrel);
-#endif
     DEIG_HIP_CHECK(hipGetLastError());
   }
   return DEIG_OK;

@@ -14,7 +14,11 @@
 // to S[i][i].  Net error vs float64 ~1e-7 * max|S|, the same order as the
 // fp32-MFMA kernel (syrk.hip), at 16/3 x its MFMA rate.
 //
-// Pipeline per row chunk (bounded workspace; chunks accumulate into S):
+// Two paths by width (kFusedMaxD below, with the measurements behind it):
+//  d <= 2048: syrks_kernel, persistent, one 512-thread block per CU, stages X as it
+//   lies in HBM (fp32 rows) and splits it in LDS - no image, one pass over all rows -
+//   then syrks_reduce_kernel and diag_corr_kernel as below;
+//  d > 2048, per row chunk (bounded workspace; chunks accumulate into S):
 //   split_kernel   X (fp32, HBM) -> XP: bf16 hi/lo image in MFMA operand order,
 //                  [32-row block][256-feature panel][slice = (octet, hi|lo)]
 //                  [feature][8 rows] - a panel's K-tile is 32 contiguous KiB -
@@ -26,13 +30,13 @@
 //                  ring buffers restaged half a K-tile at a time (segment_h: 2
 //                  phases per K-tile, waves 4-7 one barrier behind, counted
 //                  vmcnt + raw s_barrier); conflict-free ds_read_b128 reads;
-//                  (the r02-r03 K loops syrks_st_kernel / syrks_q_kernel / the
-//                  non-fused syrks_kernel: ab/syrk_split_superseded.inc, A/B
-//                  builds only)
-//   syrks_reduce   split-K remainder tiles, summed in block order (deterministic);
-//   diag_corr      S[i][i] += alpha * sum lo_i^2.
-// Tile order: 8 x 4 super-tiles of the lower triangle, so the ~32 tiles an XCD
-// runs concurrently share few panels in its L2.  Work decomposition (no
+//                  diagonal tiles read their B operands from the A quarters and skip
+//                  the MFMA blocks above the diagonal;
+//   syrks_reduce_kernel  split-K remainder tiles, summed in block order (deterministic);
+//   diag_corr_kernel  S[i][i] += alpha * sum lo_i^2.
+// Tile order: compact XCD groups where G = 256 and nt % 8 == 0
+// (tile_order_compact_kernel), else 8 x 4 super-tiles of the lower triangle, so the
+// ~32 tiles an XCD runs concurrently share few panels in its L2.  Work decomposition (no
 // atomics): q = T / G full phases of one tile per block; the R = T mod G
 // remainder tiles are cut into nseg equal K segments run K-synchronously
 // (segment-major item order) and summed in segment order by syrks_reduce.
@@ -83,12 +87,9 @@ struct SSched {
   float alpha;
   int beta;
   int flush_kt;  // K-tiles between two-level flushes of the accumulators
-  int prio;      // 1: waves 4-7 run at s_setprio 1 (the arbitration losers otherwise)
   unsigned* pace;  // per-XCD arrival counters (128 B apart), zeroed per launch
   int pace_kt;     // K-tiles between two XCD pacing points (0: off)
-  int xm;          // remainder: segments per XCD, XCD-major numbering (0: global)
-  int rpace;       // remainder rounds paced too (segment_h only)
-  // fused split (variant 163): X is staged as fp32 and split in LDS
+  // fused split: X is staged as fp32 and split in LDS
   const float* X;
   int64_t ldx, nrows;
   float* corr;  // lo^2 partials: [segment][octet wave][dp]
@@ -151,52 +152,12 @@ __device__ __forceinline__ void dma16(i32x4 rsrc, int voff, const void* lds_dst)
                : "memory", "m0");
 }
 
-// A K-tile is KT MFMA k-steps (16 rows each); the LDS ring holds NST K-tiles.
-// Panel slice sl = (octet sl/2, hi|lo sl%2) is 4 KiB = four 1-KiB DMA wave-
-// instructions; a panel has 4*KT slices.  One wave issues 4*KT DMAs per stage
-// off the diagonal (the flattened [A slices | B slices] list split over the 8
-// waves) and 2*KT on it (A only) - the counted vmcnt waits rely on these counts.
-template <int KT>
-struct Geo {
-  static constexpr int NSLICE = 4 * KT;
-  static constexpr int PANEL_B = NSLICE * SLICE_B;
-  static constexpr int BUF_B = 2 * PANEL_B;
-  static constexpr int DMA = 4 * KT, DMA_DIAG = 2 * KT;
-};
+// LDS ring geometry: a K-tile is 32 rows; a panel's K-tile is its 8 (octet, hi|lo)
+// slices = 32 KiB, a ring buffer holds the A and the B panel of one K-tile.
+constexpr int PANEL_B = 8 * SLICE_B;
+constexpr int BUF_B = 2 * PANEL_B;
 
-template <int KT>
-__device__ __forceinline__ void stage(const SSched& s, int64_t kt, int i0, int j0, bool diag,
-                                      unsigned char* buf, int wave, int lane16) {
-  using G_ = Geo<KT>;
-  // XP: [32-row block][panel][slice 0..7][256 features][16 B]; this K-tile is
-  // slices s0 .. s0 + 4*KT - 1 of block kt*KT/2.
-  const int64_t blk = kt * KT / 2;
-  const int s0 = (int)((kt * KT) & 1) * 4;
-  const i32x4 rsrc = make_rsrc(s.XP + blk * (int64_t)s.nt * BLOCK_B, (uint32_t)(s.nt * BLOCK_B));
-  int l16 = lane16;
-  asm volatile("" : "+v"(l16));
-  if (!diag) {
-#pragma unroll
-    for (int u = 0; u < KT; ++u) {
-      const int c = wave * KT + u;  // slice in [A slices | B slices]
-      const int pb = c / G_::NSLICE, sl = c % G_::NSLICE;
-      const int g = (pb ? j0 : i0) / BT * BLOCK_B + (s0 + sl) * SLICE_B;
-      unsigned char* dst = buf + pb * G_::PANEL_B + sl * SLICE_B;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) dma16(rsrc, l16 + g + p * 1024, dst + p * 1024);
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < 2 * KT; ++u) {
-      const int idx = wave * 2 * KT + u;  // (slice, 1-KiB part) of panel A
-      const int sl = idx >> 2, p = idx & 3;
-      dma16(rsrc, l16 + i0 / BT * BLOCK_B + (s0 + sl) * SLICE_B + p * 1024,
-            buf + sl * SLICE_B + p * 1024);
-    }
-  }
-}
-
-// ------------------------------------------------ fused split (variant 163)
+// ------------------------------------------------ fused split (d <= kFusedMaxD)
 // X is staged as it lies in HBM (fp32 rows) and split in LDS, so no XP image is
 // written and re-read (the split pass moved 2 x 4nd bytes).  A K-tile is 32 rows;
 // wave w owns octet w & 3 of panel w >> 2 (diagonal tiles: panel A twice): it
@@ -216,7 +177,7 @@ __device__ __forceinline__ void stage_x(const SSched& s, int64_t kt, int f0, uns
   rv = rv < 0 ? 0 : rv > 8 ? 8 : rv;
   const uint32_t ldx4 = (uint32_t)s.ldx * 4u;
   const i32x4 rsrc = make_rsrc(s.X + row0 * s.ldx + f0, (uint32_t)rv * ldx4);
-  unsigned char* dst = buf + (wave >> 2) * Geo<2>::PANEL_B + (wave & 3) * OCT_B;
+  unsigned char* dst = buf + (wave >> 2) * PANEL_B + (wave & 3) * OCT_B;
 #pragma unroll
   for (int r = 0; r < 8; ++r) dma16(rsrc, voff + (int)(r * ldx4), dst + r * 1024);
 }
@@ -230,7 +191,7 @@ __device__ __forceinline__ void stage_x(const SSched& s, int64_t kt, int f0, uns
 template <bool SQ>
 __device__ __forceinline__ void convert_x(unsigned char* buf, int wave, int lane, int rv, int fv,
                                           float* sq) {
-  unsigned char* R = buf + (wave >> 2) * Geo<2>::PANEL_B + (wave & 3) * OCT_B;
+  unsigned char* R = buf + (wave >> 2) * PANEL_B + (wave & 3) * OCT_B;
   f32x2 v[2][8];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
@@ -269,86 +230,11 @@ __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// Wait until this wave's DMAs of a stage have landed while `ahead` later stages
-// (0 .. NST-2) may stay in flight.
-template <int KT, int NST>
-__device__ __forceinline__ void wait_stage(int ahead, bool diag) {
-  static_assert(NST >= 2 && NST <= 5, "ring depth");
-  constexpr int D = Geo<KT>::DMA, DD = Geo<KT>::DMA_DIAG;
-  if (ahead <= 0) {
-    wait_vm<0>();
-  } else if (ahead == 1 || NST == 3) {
-    if (diag) wait_vm<DD>(); else wait_vm<D>();
-  } else if (ahead == 2 || NST == 4) {
-    if (diag) wait_vm<2 * DD>(); else wait_vm<2 * D>();
-  } else {
-    if (diag) wait_vm<3 * DD>(); else wait_vm<3 * D>();
-  }
-}
-
 // ---------------------------------------------------------------- accumulators
-// A wave's 128 x 64 output tile in MFMA result registers, for two MFMA shapes:
-//   MF = 32: v_mfma_f32_32x32x16_bf16, 4 x 2 blocks of f32x16;
-//   MF = 16: v_mfma_f32_16x16x32_bf16, 8 x 4 blocks of f32x4.
-// Both are viewed as 32 "quads": 4 consecutive rows ib..ib+3 of one column j,
-// which is how they are flushed, spilled to slabs and stored.
-template <int MF>
-struct Acc;
-
-template <>
-struct Acc<32> {
-  f32x16 a[4][2];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[mb][nb][r] = 0.f;
-  }
-  // quad q = (mb, nb, g): rows 32 mb + 8 g + 4 (lane / 32), column 32 nb + lane % 32
-  __device__ __forceinline__ float at(int q, int u) const { return a[q >> 3][(q >> 2) & 1][4 * (q & 3) + u]; }
-  __device__ __forceinline__ void set(int q, int u, float v) { a[q >> 3][(q >> 2) & 1][4 * (q & 3) + u] = v; }
-  static __device__ __forceinline__ int qrow(int q, int lane) {
-    return 32 * (q >> 3) + 8 * (q & 3) + 4 * (lane >> 5);
-  }
-  static __device__ __forceinline__ int qcol(int q, int lane) { return 32 * ((q >> 2) & 1) + (lane & 31); }
-
-  // One K-tile of KT 16-row k-steps; operand slice of 8 k-values: octet 2 st + lane / 32.
-  template <int KT>
-  __device__ __forceinline__ void mma(const unsigned char* A, const unsigned char* B, int wi,
-                                      int wj, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int st = 0; st < KT; ++st) {
-      const int o = 2 * st + h;
-      const unsigned char* ph = A + ((o * 2) * BT + 128 * wi + c) * 16;
-      const unsigned char* qh = B + ((o * 2) * BT + 64 * wj + c) * 16;
-      bf16x8 ahi[4], alo[4], bhi[2], blo[2];
-#pragma unroll
-      for (int mb = 0; mb < 4; ++mb) {
-        ahi[mb] = *reinterpret_cast<const bf16x8*>(ph + (32 * mb) * 16);
-        alo[mb] = *reinterpret_cast<const bf16x8*>(ph + (BT + 32 * mb) * 16);
-      }
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        bhi[nb] = *reinterpret_cast<const bf16x8*>(qh + (32 * nb) * 16);
-        blo[nb] = *reinterpret_cast<const bf16x8*>(qh + (BT + 32 * nb) * 16);
-      }
-#pragma unroll
-      for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-          a[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mb], bhi[nb], a[mb][nb], 0, 0, 0);
-          a[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mb], blo[nb], a[mb][nb], 0, 0, 0);
-          a[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo[mb], bhi[nb], a[mb][nb], 0, 0, 0);
-        }
-    }
-  }
-};
-
-template <>
-struct Acc<16> {
+// A wave's 128 x 64 output tile in the result registers of v_mfma_f32_16x16x32_bf16:
+// 8 x 4 blocks of f32x4, viewed as 32 "quads" - 4 consecutive rows ib..ib+3 of one
+// column j - which is how they are flushed, spilled to slabs and stored.
+struct Acc {
   f32x4 a[8][4];
   __device__ __forceinline__ void zero() {
 #pragma unroll
@@ -362,16 +248,12 @@ struct Acc<16> {
   static __device__ __forceinline__ int qrow(int q, int lane) { return 16 * (q >> 2) + 4 * (lane >> 4); }
   static __device__ __forceinline__ int qcol(int q, int lane) { return 16 * (q & 3) + (lane & 15); }
 
-  // One K-tile of KT 16-row k-steps = KT/2 32-deep MFMA steps; operand slice of
-  // 8 k-values: octet 4 st + lane / 16 (conflict-free ds_read_b128 lane groups).
-  template <int KT>
+  // One K-tile (32 rows) = one 32-deep MFMA step; operand slice of 8 k-values:
+  // octet lane / 16 (conflict-free ds_read_b128 lane groups).
   __device__ __forceinline__ void mma(const unsigned char* A, const unsigned char* B, int wi,
                                       int wj, int lane) {
-    static_assert(KT % 2 == 0, "16x16x32 needs 32-row K-tiles");
-    const int c = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int st = 0; st < KT / 2; ++st) {
-      const int o = 4 * st + g;
+    const int c = lane & 15, o = lane >> 4;
+    {
       const unsigned char* ph = A + ((o * 2) * BT + 128 * wi + c) * 16;
       const unsigned char* qh = B + ((o * 2) * BT + 64 * wj + c) * 16;
       bf16x8 bhi[4], blo[4];
@@ -413,7 +295,6 @@ struct Acc<16> {
       }
     }
   }
-
 };
 
 constexpr int NQUAD = 32;
@@ -425,21 +306,6 @@ __device__ __forceinline__ f32x4* slab_at(float* slab, int wave, int q, int lane
 
 // The slab addresses are formed here from an opaque base: otherwise the compiler
 // hoists all 32 of them out of the K loop and keeps 64 VGPRs live for them.
-#ifdef DEIG_AB_SYRK_SERIAL_FLUSH
-template <int MF>
-__device__ __forceinline__ void flush(float* slab, bool first, Acc<MF>& acc, int wave, int lane) {
-  asm volatile("" : "+v"(slab));
-#pragma unroll
-  for (int q = 0; q < NQUAD; ++q) {
-    f32x4* ptr = slab_at(slab, wave, q, lane);
-    f32x4 v = {acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    if (!first) v += *ptr;
-    *ptr = v;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc.set(q, u, 0.f);
-  }
-}
-#else
 // r06: buffer loads / stores in batches of kFlushBatch quads.  Through a generic
 // pointer the slab accesses were flat_* operations, which the hardware may complete
 // out of order, so each quad's read was its own vmcnt(0) round trip: 32 serial round
@@ -451,8 +317,7 @@ constexpr int kFlushBatch = DEIG_AB_SYRK_FLUSH_BATCH;
 #else
 constexpr int kFlushBatch = 4;
 #endif
-template <int MF>
-__device__ __forceinline__ void flush(float* slab, bool first, Acc<MF>& acc, int wave, int lane) {
+__device__ __forceinline__ void flush(float* slab, bool first, Acc& acc, int wave, int lane) {
   asm volatile("" : "+v"(slab));
   const __amdgpu_buffer_rsrc_t r =
       __builtin_amdgcn_make_buffer_rsrc(slab, (short)0, (int)(SLAB * sizeof(float)), 0x00020000);
@@ -482,19 +347,9 @@ __device__ __forceinline__ void flush(float* slab, bool first, Acc<MF>& acc, int
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-#endif
 
-template <int MF>
-__device__ __forceinline__ void unflush(float* slab, Acc<MF>& acc, int wave, int lane) {
+__device__ __forceinline__ void unflush(float* slab, Acc& acc, int wave, int lane) {
   asm volatile("" : "+v"(slab));
-#ifdef DEIG_AB_SYRK_SERIAL_FLUSH
-#pragma unroll
-  for (int q = 0; q < NQUAD; ++q) {
-    const f32x4 v = *slab_at(slab, wave, q, lane);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc.set(q, u, acc.at(q, u) + v[u]);
-  }
-#else
   // buffer loads in batches (flat loads were one vmcnt(0) round trip each, see flush)
   const __amdgpu_buffer_rsrc_t r =
       __builtin_amdgcn_make_buffer_rsrc(slab, (short)0, (int)(SLAB * sizeof(float)), 0x00020000);
@@ -511,7 +366,6 @@ __device__ __forceinline__ void unflush(float* slab, Acc<MF>& acc, int wave, int
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc.set(b + i, u, acc.at(b + i, u) + v[i][u]);
   }
-#endif
 }
 
 // Store 4 consecutive rows ib..ib+3 of column j (values = alpha * a[u] (+ S)),
@@ -541,10 +395,10 @@ __device__ __forceinline__ void store4(const SSched& s, int ib, int j, bool diag
   }
 }
 
-template <int MF, int KT, int NST, bool FX, bool SQ>
+// One work item of the fused kernel: K-tiles [k0, k1) of a tile on a two-stage ring.
+template <bool SQ>
 __device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int tile, int64_t k0, int64_t k1,
                         int slot, bool partial, int pace_j, int cseg) {
-  static_assert(!FX || (KT == 2 && NST == 2), "fused split: 32-row K-tiles, two stages");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wi = wave >> 2, wj = wave & 3;
@@ -561,8 +415,7 @@ __device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int
   const bool sqw = SQ;
   float sq[4] = {0.f, 0.f, 0.f, 0.f};
 
-  if (s.prio && wave >= 4) __builtin_amdgcn_s_setprio(1);
-  Acc<MF> acc;
+  Acc acc;
   acc.zero();
   float* slab = partial ? s.part + (int64_t)slot * SLAB : s.accs + (int64_t)blockIdx.x * SLAB;
   bool flushed = false;
@@ -572,71 +425,54 @@ __device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int
     // counted waits assume only DMAs): drain the previous segment's stores.
     wait_vm<0>();
     __syncthreads();  // the previous segment's last stage may still be read
-    // Ring of NST stages; NST - 1 K-tiles are issued ahead of the one being
-    // computed.  Stage t lives in buffer t % NST.
-    constexpr int BUF_B = Geo<KT>::BUF_B;
-    if constexpr (FX) {
-      // fused: K-tile k0 staged and split (masked: it may be ragged) before the
-      // loop; iteration t stages K-tile t + 1 after the barrier and splits it
-      // inside K-tile t's MFMAs (its own region: a vmcnt wait, no barrier).
-      stage_x(s, k0, fx0, lds, wave, xvoff);
-      wait_vm<0>();
-      const int64_t rv0 = s.nrows - (k0 * 32 + 8 * (wave & 3));
-      convert_x<SQ>(lds, wave, lane, rv0 < 0 ? 0 : rv0 > 8 ? 8 : (int)rv0, fv, sq);
-    } else {
-      for (int t = 0; t < NST - 1 && t < nkt; ++t)
-        stage<KT>(s, k0 + t, i0, j0, diag, lds + t * BUF_B, wave, lane16);
-    }
-    int cur = 0, nxt = NST - 1, since = 0, since_pace = 0;
+    // Ring of two stages: stage t lives in buffer t % 2.  K-tile k0 is staged and
+    // split (masked: it may be ragged) before the loop; iteration t stages K-tile
+    // t + 1 after the barrier and splits it inside K-tile t's MFMAs (its own region:
+    // a vmcnt wait, no barrier).
+    stage_x(s, k0, fx0, lds, wave, xvoff);
+    wait_vm<0>();
+    const int64_t rv0 = s.nrows - (k0 * 32 + 8 * (wave & 3));
+    convert_x<SQ>(lds, wave, lane, rv0 < 0 ? 0 : rv0 > 8 ? 8 : (int)rv0, fv, sq);
+    int cur = 0, nxt = 1, since = 0, since_pace = 0;
     // pacing target: blocks on this XCD x arrival index
     const int xcd = blockIdx.x & 7;
     const unsigned nx = (unsigned)((s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0));
     for (int64_t t = 0; t < nkt; ++t) {
-      const int64_t left = nkt - 1 - t;
       if (pace_j >= 0 && ++since_pace == s.pace_kt) {
         since_pace = 0;
         ++pace_j;
         if (threadIdx.x == 0) xcd_pace(s.pace + 32 * xcd, (unsigned)pace_j * nx);
       }
-      // RAW: this wave's DMAs of stage t landed (counted vmcnt), then a barrier
-      // every reader passes.  WAR: stage t-1's ds_reads retired (lgkmcnt) before
-      // the barrier, so its buffer can be restaged right after it.  A raw
-      // s_barrier: __syncthreads() would drain the ring with vmcnt(0).
-      // fused: every wave split its own region of stage t last iteration (its
+      // RAW: every wave split its own region of stage t last iteration (its
       // ds_writes retire at the lgkmcnt wait), so the barrier publishes stage t.
-      if (!FX) wait_stage<KT, NST>(left < NST - 2 ? (int)left : NST - 2, diag);
+      // WAR: stage t-1's ds_reads retired (lgkmcnt) before the barrier, so its
+      // buffer can be restaged right after it.  A raw s_barrier: __syncthreads()
+      // would also wait for vmcnt(0).
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if constexpr (FX) {
-        if (t + 1 < nkt) stage_x(s, k0 + t + 1, fx0, lds + nxt * BUF_B, wave, xvoff);
-        // K-tile t's MFMAs, then this wave's split of K-tile t + 1 (its DMAs were
-        // issued right after the barrier: the MFMAs cover their latency).  The
-        // in-place split of the wave's own region needs no barrier of its own.
-        unsigned char* bc = lds + cur * BUF_B;
-        acc.template mma<KT>(bc, bc + Geo<KT>::PANEL_B, wi, wj, lane);
-        if (t + 1 < nkt) {
-          wait_vm<0>();
-          const int64_t rv1 = s.nrows - ((k0 + t + 1) * 32 + 8 * (wave & 3));
-          convert_x<SQ>(lds + nxt * BUF_B, wave, lane, rv1 < 0 ? 0 : rv1 > 8 ? 8 : (int)rv1, fv, sq);
-        }
-      } else {
-        if (t + NST - 1 < nkt)
-          stage<KT>(s, k0 + t + NST - 1, i0, j0, diag, lds + nxt * BUF_B, wave, lane16);
-        unsigned char* bc = lds + cur * BUF_B;
-        acc.template mma<KT>(bc, diag ? bc : bc + Geo<KT>::PANEL_B, wi, wj, lane);
+      if (t + 1 < nkt) stage_x(s, k0 + t + 1, fx0, lds + nxt * BUF_B, wave, xvoff);
+      // K-tile t's MFMAs, then this wave's split of K-tile t + 1 (its DMAs were
+      // issued right after the barrier: the MFMAs cover their latency).  The
+      // in-place split of the wave's own region needs no barrier of its own.
+      unsigned char* bc = lds + cur * BUF_B;
+      acc.mma(bc, bc + PANEL_B, wi, wj, lane);
+      if (t + 1 < nkt) {
+        wait_vm<0>();
+        const int64_t rv1 = s.nrows - ((k0 + t + 1) * 32 + 8 * (wave & 3));
+        convert_x<SQ>(lds + nxt * BUF_B, wave, lane, rv1 < 0 ? 0 : rv1 > 8 ? 8 : (int)rv1, fv, sq);
       }
       if (++since == s.flush_kt && t + 1 < nkt) {
-        flush<MF>(slab, !flushed, acc, wave, lane);
+        flush(slab, !flushed, acc, wave, lane);
         wait_vm<0>();  // keep the slab traffic off the ring's counted waits
         flushed = true;
         since = 0;
       }
-      cur = cur + 1 == NST ? 0 : cur + 1;
-      nxt = nxt + 1 == NST ? 0 : nxt + 1;
+      cur = cur + 1 == 2 ? 0 : cur + 1;
+      nxt = nxt + 1 == 2 ? 0 : nxt + 1;
     }
   }
-  if (flushed) unflush<MF>(slab, acc, wave, lane);
+  if (flushed) unflush(slab, acc, wave, lane);
   if (sqw) {  // [segment][octet wave][dp]; summed by diag_corr_kernel
     float* c = s.corr + (int64_t)(cseg * 4 + wave) * s.dp + i0;
 #pragma unroll
@@ -653,14 +489,9 @@ __device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int
 #pragma unroll
   for (int q = 0; q < NQUAD; ++q) {
     const float a[4] = {acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    store4(s, i0 + 128 * wi + Acc<MF>::qrow(q, lane), j0 + 64 * wj + Acc<MF>::qcol(q, lane), diag, a);
+    store4(s, i0 + 128 * wi + Acc::qrow(q, lane), j0 + 64 * wj + Acc::qcol(q, lane), diag, a);
   }
 }
-
-#ifdef DEIG_AB_SYRK_VARIANT
-// the r03 K loops (staggered phases, quarter-refill ring): A/B builds only
-#include "ab/syrk_split_superseded.inc"
-#endif
 
 // Pacing points of one segment: point j (1..n) waits for the XCD counter to reach
 // base + j * mult (n = 0: none).
@@ -672,15 +503,9 @@ struct PaceSeq {
   bool g = false;      // every kChipPaceEvery-th point is also chip-wide
 };
 
-// Blocks of this block's XCD (logical L) that run a remainder item in round u.
-// Global numbering: item i = L + u G (the XCD's blocks are logical [L - b/8, + nx));
-// XCD-major (s.xm > 0, G % 8 == 0): XCD x owns segments [x xm, (x + 1) xm) and its
-// G / 8 blocks take their items j = l + u G / 8 (j = local segment * R + r).
+// Blocks of this block's XCD (logical L) that run a remainder item in round u: item
+// i = L + u G (the XCD's blocks are logical [L - b/8, + nx)).
 __device__ __forceinline__ int rem_active(const SSched& s, int L, int u) {
-  if (s.xm) {
-    const int gx = s.G >> 3, left = s.R * s.xm - u * gx;
-    return left < 0 ? 0 : (left < gx ? left : gx);
-  }
   const int xcd = blockIdx.x & 7;
   const int nx = (s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0);
   const int left = s.R * s.nseg - u * s.G - (L - (int)(blockIdx.x >> 3));
@@ -688,34 +513,23 @@ __device__ __forceinline__ int rem_active(const SSched& s, int L, int u) {
 }
 
 __device__ __forceinline__ int rem_rounds(const SSched& s, int L) {
-  if (s.xm) {
-    const int gx = s.G >> 3, l = L % gx, items = s.R * s.xm;
-    return l < items ? (items - 1 - l) / gx + 1 : 0;
-  }
   const int items = s.R * s.nseg;
   return L < items ? (items - 1 - L) / s.G + 1 : 0;
 }
 
 // Round u's item of block L: tile index, slot (= segment * R + r) and segment.
 __device__ __forceinline__ void rem_item(const SSched& s, int L, int u, int& tile, int& slot, int& sg) {
-  int r;
-  if (s.xm) {
-    const int gx = s.G >> 3, x = L / gx, j = L - x * gx + u * gx;
-    const int sl = j / s.R;
-    r = j - sl * s.R;
-    sg = x * s.xm + sl;
-  } else {
-    const int i = L + u * s.G;
-    sg = i / s.R;
-    r = i - sg * s.R;
-  }
+  const int i = L + u * s.G;
+  sg = i / s.R;
+  const int r = i - sg * s.R;
   tile = s.q * s.G + r;
   slot = sg * s.R + r;
 }
 
-// ------------------------------------------------ half-refill ring (variant 30000)
-// The staggered kernel's two phases per K-tile (variant 12100: 48-MFMA M parts, half
-// the barriers of four phases) on segment_q's ring: phase h reads A quarters 2h and
+// ------------------------------------------------ half-refill ring (d > kFusedMaxD)
+// Two phases per K-tile (48-MFMA M parts), waves 4-7 one barrier behind waves 0-3: a
+// ring buffer is four A quarters (8 KiB: features 32 q .. 32 q + 31 and 128 + the same
+// of all 8 slices) and the B panel; phase h reads A quarters 2h and
 // 2h + 1 (and B in phase 0), and each region is restaged with K-tile t + 2 as soon as
 // both wave groups have read it.  Per wave and K-tile 8 pieces in two L parts of 4:
 //   L_0(t): B(t+1) parts 2, 3 and A quarters 2, 3 of t+1 into nxt (their previous
@@ -729,7 +543,7 @@ __device__ __forceinline__ void rem_item(const SSched& s, int L, int u, int& til
 // B part 3 issued in L_0(t): quarters 2, 3 of t+1 + L_1(t)'s 4 = 6).  Near the end of
 // the segment the counts shrink with the pieces not issued.  WAR: every L part
 // retires its reads (lgkmcnt(0)) before its closing barrier.  Same MFMA order per
-// accumulator as the other variants (bit-identical sums).
+// accumulator as the fused kernel (Acc::mma).
 // DW != -1: a DIAGONAL tile.  Its B panel is its A panel, so no B pieces are staged
 // and the B operands are read from the A quarters (the same bytes in the A layout);
 // with 2 DMA pieces per L part instead of 4 the counted waits become 4 / 2, and the end
@@ -752,16 +566,11 @@ constexpr bool dw_row(int dw, int mb) { return !dw_skip(dw, mb, 0); }  // A bloc
 constexpr bool dw_col(int dw, int nb) { return !dw_skip(dw, 7, nb); }  // B block column nb is read
 constexpr bool dw_idle(int dw) { return !dw_row(dw, 7); }
 
-template <int PRIO, int DW>
+template <int DW>
 __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, int tile, int64_t k0,
                                           int64_t k1, int slot, bool partial, const PaceSeq& pc) {
   constexpr bool idle = dw_idle(DW);
-#ifndef DEIG_AB_SYRK_DIAG_B_DMA
   constexpr bool dgb = DW != kDwOff;  // B operands from the A quarters
-#else
-  constexpr bool dgb = false;
-#endif
-  constexpr int BUF_B = Geo<2>::BUF_B;
   constexpr int QB = 8 * 1024;  // one A quarter
   constexpr int BOFF = 4 * QB;  // the B panel
   const int lane = threadIdx.x & 63;
@@ -772,7 +581,7 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
   const int ti = tt & 0xffff, tj = tt >> 16;
   const int i0 = ti * BT, j0 = tj * BT;
   const bool diag = (ti == tj);
-  Acc<16> acc;
+  Acc acc;
   acc.zero();
   float* slab = partial ? s.part + (int64_t)slot * SLAB : s.accs + (int64_t)blockIdx.x * SLAB;
   bool flushed = false;
@@ -859,7 +668,7 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
             }
           }
           if (since == s.flush_kt) {
-            if constexpr (!idle) flush<16>(slab, !flushed, acc, wave, lane);
+            if constexpr (!idle) flush(slab, !flushed, acc, wave, lane);
             wait_vm<0>();
             flushed = true;
             since = 0;
@@ -910,7 +719,6 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bar();
         // ---------------- M part
-        if (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const int mb = 4 * h + m;
@@ -927,13 +735,12 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
             if (!dw_skip(DW, mb, nb))
               acc.a[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[m], bhi[nb], acc.a[mb][nb], 0, 0, 0);
         }
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
         bar();
       }
     }
     if (!lag) bar();  // balance the stagger
   }
-  if (flushed && !idle) unflush<16>(slab, acc, wave, lane);
+  if (flushed && !idle) unflush(slab, acc, wave, lane);
   if (partial) {
 #pragma unroll
     for (int q = 0; q < NQUAD; ++q)
@@ -944,22 +751,21 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
 #pragma unroll
   for (int q = 0; q < NQUAD; ++q) {
     const float a[4] = {acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    store4(s, i0 + 128 * wi + Acc<16>::qrow(q, lane), j0 + 64 * wj + Acc<16>::qcol(q, lane), diag, a);
+    store4(s, i0 + 128 * wi + Acc::qrow(q, lane), j0 + 64 * wj + Acc::qcol(q, lane), diag, a);
   }
 }
 
-template <int PRIO>
 __global__ __launch_bounds__(NTHR) void syrks_h_kernel(SSched s) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * Geo<2>::BUF_B];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_B];
   const int L = xcd_logical(blockIdx.x, s.G);
   const int nwork = s.q + rem_rounds(s, L);
   const int xcd = blockIdx.x & 7;
   const unsigned nx = (unsigned)((s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0));
-  // Full phases: every block runs P = NK / pace_kt points per tile.  Remainder rounds
-  // (rpace): Pm points per item, Pm from the shortest segment, so every item of a
+  // Full phases: every block runs P = NK / pace_kt points per tile.  Remainder rounds:
+  // Pm points per item, Pm from the shortest segment, so every item of a
   // round runs the same count and the targets stay exact across rounds.
   const unsigned P = s.pace_kt > 0 ? (unsigned)(s.NK / s.pace_kt) : 0u;
-  const int Pm = (s.pace_kt > 0 && s.rpace && s.nseg > 0) ? (int)(s.NK / s.nseg / s.pace_kt) : 0;
+  const int Pm = (s.pace_kt > 0 && s.nseg > 0) ? (int)(s.NK / s.nseg / s.pace_kt) : 0;
   unsigned rbase = (unsigned)s.q * P * nx;
   for (int w = 0; w < nwork; ++w) {
     int tile, slot = 0, sg = 0;
@@ -980,42 +786,36 @@ __global__ __launch_bounds__(NTHR) void syrks_h_kernel(SSched s) {
         unsigned before = 0;
         for (int u = 0; u < w - s.q; ++u) before += (unsigned)rem_active(s, L, u);
         pc = PaceSeq{Pm, rbase + before * (unsigned)Pm, (unsigned)rem_active(s, L, w - s.q)};
-#ifndef DEIG_AB_SYRK_NO_REM_CHIP
-        if (!s.xm) {  // global item numbering: round u runs min(G, items - u G) items
-          const int items = s.R * s.nseg;
-          unsigned gb = (unsigned)s.q * (P / kChipPaceEvery) * (unsigned)s.G;
-          for (int u = 0; u < w - s.q; ++u)
-            gb += (unsigned)min(s.G, items - u * s.G) * (unsigned)(Pm / kChipPaceEvery);
-          pc.g = true;
-          pc.gbase = gb;
-          pc.gmult = (unsigned)min(s.G, items - (w - s.q) * s.G);
-        }
-#endif
+        // chip-wide: round u runs min(G, items - u G) items
+        const int items = s.R * s.nseg;
+        unsigned gb = (unsigned)s.q * (P / kChipPaceEvery) * (unsigned)s.G;
+        for (int u = 0; u < w - s.q; ++u)
+          gb += (unsigned)min(s.G, items - u * s.G) * (unsigned)(Pm / kChipPaceEvery);
+        pc.g = true;
+        pc.gbase = gb;
+        pc.gmult = (unsigned)min(s.G, items - (w - s.q) * s.G);
       }
     }
     const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool dg = (tt & 0xffff) == (tt >> 16);
-#ifndef DEIG_AB_SYRK_NO_DIAG_IDLE
     const int dw = 64 * (wv & 3) - 128 * (wv >> 2);
     if (dg && dw == 0)
-      segment_h<PRIO, 0>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<0>(s, lds, tile, k0, k1, slot, partial, pc);
     else if (dg && dw == 64)
-      segment_h<PRIO, 64>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<64>(s, lds, tile, k0, k1, slot, partial, pc);
     else if (dg && dw >= 128)  // waves 2 and 3: the whole block above the diagonal
-      segment_h<PRIO, 128>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<128>(s, lds, tile, k0, k1, slot, partial, pc);
     else if (dg)
-      segment_h<PRIO, kDwDiag>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<kDwDiag>(s, lds, tile, k0, k1, slot, partial, pc);
     else
-#endif
-      segment_h<PRIO, kDwOff>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<kDwOff>(s, lds, tile, k0, k1, slot, partial, pc);
   }
 }
 
-template <int MF, int KT, int NST, bool FX>
+// The fused-split kernel (d <= kFusedMaxD): persistent, one block per CU.
 __global__ __launch_bounds__(NTHR) void syrks_kernel(SSched s) {
-  static_assert(NST * Geo<KT>::BUF_B <= 160 * 1024, "LDS ring exceeds 160 KiB");
-  __shared__ __attribute__((aligned(16))) unsigned char lds[NST * Geo<KT>::BUF_B];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_B];
   const int b = blockIdx.x;
   const int L = xcd_logical(b, s.G);
   // Full phases (w < q): every block walks all K of one tile, in lock-step with
@@ -1024,7 +824,6 @@ __global__ __launch_bounds__(NTHR) void syrks_kernel(SSched s) {
   // keeps the items that run together (and, by the XCD-aware relabel, the ~G/8
   // on one XCD) on the same K rows of neighbouring tiles, so their panels are
   // shared in L2 rather than each item streaming its own K range from HBM.
-  // One call site of segment(): its unrolled body is inlined once.
   const int items = s.R * s.nseg;
   const int nwork = s.q + (L < items ? (items - 1 - L) / s.G + 1 : 0);
   for (int w = 0; w < nwork; ++w) {
@@ -1046,22 +845,17 @@ __global__ __launch_bounds__(NTHR) void syrks_kernel(SSched s) {
     }
     // full phases pace (identical K work on every block); remainder items do not
     const int pace_j = (!partial && s.pace_kt > 0) ? (int)(w * (s.NK / s.pace_kt)) : -1;
-    // fused: the lo^2 accumulation is compiled only into the copy that the
-    // diagonal tiles' A-panel waves run
-    if constexpr (FX) {
-      const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
-      if ((tt & 0xffff) == (tt >> 16) && (threadIdx.x >> 6) < 4)
-        segment<MF, KT, NST, true, true>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
-      else
-        segment<MF, KT, NST, true, false>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
-    } else {
-      segment<MF, KT, NST, false, false>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
-    }
+    // the lo^2 accumulation is compiled only into the copy that the diagonal tiles'
+    // A-panel waves run
+    const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
+    if ((tt & 0xffff) == (tt >> 16) && (threadIdx.x >> 6) < 4)
+      segment<true>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
+    else
+      segment<false>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
   }
 }
 
 // grid (R, SLAB/4/256): one thread per float4 of a remainder tile's slab image.
-template <int MF>
 __global__ __launch_bounds__(256) void syrks_reduce_kernel(SSched s) {
   const int r = blockIdx.x;
   const int f = blockIdx.y * 256 + threadIdx.x;
@@ -1074,7 +868,7 @@ __global__ __launch_bounds__(256) void syrks_reduce_kernel(SSched s) {
   for (int sg = 0; sg < s.nseg; ++sg)  // fixed order: deterministic
     sum += *reinterpret_cast<const f32x4*>(s.part + (int64_t)(sg * s.R + r) * SLAB + (int64_t)f * 4);
   const float a[4] = {sum[0], sum[1], sum[2], sum[3]};
-  store4(s, ti * BT + 128 * wi + Acc<MF>::qrow(q, lane), tj * BT + 64 * wj + Acc<MF>::qcol(q, lane),
+  store4(s, ti * BT + 128 * wi + Acc::qrow(q, lane), tj * BT + 64 * wj + Acc::qcol(q, lane),
          diag, a);
 }
 
@@ -1230,35 +1024,8 @@ __global__ __launch_bounds__(256) void tile_order_compact_kernel(int nt, int* or
   }
 }
 
-// Remainder schedule of the half-ring kernel: bit 0 paces remainder rounds, bit 1
-// numbers remainder items XCD-major.  Default 1 since r04 (interleaved A/B in one
-// process, profiles/r04za_syrk_*_ab.log, unpaced / paced / XCD-major / both): config 2
-// (d = 3072, all 78 tiles remainder) 26.84 / 26.13 / 27.15 / 26.34 ms; d = 4096 22.78 /
-// 22.45 / 23.37 / 22.58; d = 5120 71.8 / 66.7 / 72.6 / 66.1; config-3 shard 303.5 /
-// 305.0 / 305.0 / 304.1 (its 16 remainder tiles are 1/33 of the work; the XCD-major
-// build runs the same schedule there, so ~1.5 ms is the spread).  Unpaced, the blocks
-// of a remainder round drift apart over their ~2500 K-tiles as the full phases' did
-// (XCD pacing above); XCD-major numbering (each XCD's blocks on K ranges no other XCD
-// reads) costs more in balance (nseg a multiple of 8) than it saves in L2 misses.
-#ifdef DEIG_AB_SYRK_REM
-constexpr int kSyrkRem = DEIG_AB_SYRK_REM;
-#else
-constexpr int kSyrkRem = 1;
-#endif
-int syrk_variant(int64_t d);
-
-// XCD-major remainder: segments per XCD (<= 8) whose critical path
-// ceil(R xm / gx) / (8 xm) is within 2 % of the best.
-int xcd_segments(int64_t R, int gx) {
-  double best = 1e30;
-  for (int k = 1; k <= 8; ++k) best = fmin(best, (double)cdiv(R * k, gx) / (8 * k));
-  for (int k = 1; k <= 8; ++k)
-    if ((double)cdiv(R * k, gx) / (8 * k) <= best * 1.02) return k;
-  return 1;
-}
-
 struct Layout {
-  int64_t dp, nt, T, G, q, R, nseg, xm, yb_max, chunk_rows;
+  int64_t dp, nt, T, G, q, R, nseg, yb_max, chunk_rows;
   size_t off_order, off_pace, off_accs, off_part, off_corr, off_xp, total;
 };
 
@@ -1272,11 +1039,6 @@ Layout make_layout(int64_t n, int64_t d, int G, int64_t chunk_rows) {
   L.q = L.T / G;
   L.R = L.T % G;
   L.nseg = remainder_segments(L.R, G);
-  L.xm = 0;
-  if ((kSyrkRem & 2) && syrk_variant(d) % 100000 >= 30000 && G % 8 == 0 && L.R > 0) {
-    L.xm = xcd_segments(L.R, G / 8);
-    L.nseg = 8 * L.xm;
-  }
   L.yb_max = SPLIT_YB;
   L.chunk_rows = chunk_rows;
   size_t off = 0;
@@ -1305,74 +1067,25 @@ int64_t default_chunk_rows(int64_t n, int64_t d) {
   return n32 < cap ? n32 : cap;
 }
 
-// Kernel shape: 163 = fused split (X staged as fp32 and split in LDS), 162 = split
-// pass + MFMA 16x16x32, 22 / 13 | 14 | 15 = split pass + 32x32x16 (2 k-steps per
-// K-tile x 2 stages; 1 k-step x 3 | 4 | 5 stages).  Default by width: the fused
-// split re-splits each panel once per tile that reads it (~d / 256 times), the
-// split pass once (2 x 4nd bytes), so the split pass's share of the op falls as
-// 1/d while the fused split's stays.  Measured (r02, interleaved A/B in one
-// process, profiles/r02l_syrk_fused_ab.log): d = 3072 (config 2) fused 27.3 ms vs
-// 29.0 ms; d = 8192 (config 3 shard) fused 370 ms vs 336 ms.
-// A/B builds (tools/, never the shipped library) fix one with -DDEIG_AB_SYRK_VARIANT=N.
-// Staggered-phase variants are 1PQR0: P phases per K-tile, the next K-tile's
-// pieces over Q of them, R = 1: s_setprio(1) around the MFMA clusters; 20DR0: the
-// quarter-refill ring (segment_q) with DMA schedule D; 30000: the two-phase half-
-// refill ring (segment_h).  Default 30000 since r04 (config-3 shard, interleaved A/B in
-// one process, bit-identical, two orders on one box: 310.6 / 312.6 ms against 316.2 /
-// 319.3 for two staggered phases 12100 and 322.3 / 322.0 for the r03 default 20100,
-// profiles/r04w_syrk_half_ring_ab*.log): two phases halve the barriers per K-tile and
-// their 48-MFMA M parts cover the L parts' DMA issue (12100 alone: 311.0 vs 318.0 ms
-// for 20100 on another box; four phases 14100 / 14300 350 / 331, eight 360-366 ms,
-// s_setprio 12110 323.5, profiles/r04t_*, r04u_*), and the half ring gives every piece
-// ~1.5 K-tiles of lead instead of one.  History: r03 20000 315.3 vs 14200 319.6 ms,
-// profiles/r03f_syrk_qring_insplit_ab.log; 20100 318.5 vs 20000 323.7 ms,
-// profiles/r03l_syrk_dma_schedule_ab.log.  + 100000 * KO adds the knock-outs
-// (measurement builds only; the half ring has none).
-// The fused split up to d = 2048 since r04 (was 4096): with the half-refill ring the
-// split pass wins above (interleaved A/B, profiles/r04y_syrk_*_ab.log: config 2, d =
-// 3072, 26.9 vs 28.8 ms; d = 4096 22.7 vs 25.3; d = 2048 26.10 vs 26.09 - a tie, and
-// the fused path needs no image of the shard in the workspace).
+// Kernel by width.  d <= kFusedMaxD: the fused split (syrks_kernel: X staged as fp32
+// and split in LDS); above: split pass + half-refill ring (split_kernel,
+// syrks_h_kernel).  The fused split re-splits each panel once per tile that reads it
+// (~d / 256 times), the split pass once (2 x 4nd bytes), so the split pass's share of
+// the op falls as 1/d while the fused split's stays.  Measured (r04, interleaved A/B in
+// one process, profiles/r04y_syrk_*_ab.log): config 2, d = 3072, split pass 26.9 vs
+// fused 28.8 ms; d = 4096 22.7 vs 25.3; d = 2048 26.10 vs 26.09 - a tie, and the fused
+// path needs no image of the shard in the workspace.  (r02, before the half-refill
+// ring, profiles/r02l_syrk_fused_ab.log: d = 3072 fused 27.3 vs 29.0 ms; d = 8192
+// fused 370 vs 336 ms.)
+// The half-refill ring against the K loops it replaced (r04, config-3 shard,
+// interleaved A/B in one process, bit-identical, two orders on one box,
+// profiles/r04w_syrk_half_ring_ab*.log): 310.6 / 312.6 ms against 316.2 / 319.3 for two
+// staggered phases on a whole-K-tile ring and 322.3 / 322.0 for the r03 quarter-refill
+// ring: two phases halve the barriers per K-tile and their 48-MFMA M parts cover the L
+// parts' DMA issue (four phases 350 / 331 ms, eight 360-366 ms, s_setprio around the
+// MFMA clusters 323.5 vs 311.0, profiles/r04t_*, r04u_*), and the half ring gives every
+// piece ~1.5 K-tiles of lead instead of one.
 constexpr int64_t kFusedMaxD = 2048;
-#ifdef DEIG_AB_SYRK_VARIANT
-constexpr int kSyrkLarge = DEIG_AB_SYRK_VARIANT;
-#else
-constexpr int kSyrkLarge = 30000;
-#endif
-int syrk_variant(int64_t d) {
-#ifdef DEIG_AB_SYRK_VARIANT
-  (void)d;
-  return DEIG_AB_SYRK_VARIANT;
-#else
-  return d <= kFusedMaxD ? 163 : kSyrkLarge;
-#endif
-}
-
-// The split-pass kernel of variant V (instantiated for kSyrkLarge only).
-template <int V>
-void launch_split_pass_kernel(int G, hipStream_t stream, const SSched& s) {
-  if constexpr (V % 100000 >= 30000) {
-    hipLaunchKernelGGL((syrks_h_kernel<(V / 10) % 10>), dim3(G), dim3(NTHR), 0, stream, s);
-  }
-#ifdef DEIG_AB_SYRK_VARIANT
-  else if constexpr (V % 100000 >= 20000) {
-    hipLaunchKernelGGL((syrks_q_kernel<(V / 10) % 10, V / 100000, (V / 100) % 10>), dim3(G), dim3(NTHR), 0,
-                       stream, s);
-  } else if constexpr (V >= 10000) {
-    hipLaunchKernelGGL((syrks_st_kernel<(V / 1000) % 10, (V / 100) % 10, (V / 10) % 10, V / 100000>), dim3(G),
-                       dim3(NTHR), 0, stream, s);
-  } else if constexpr (V == 13 || V == 14 || V == 15) {
-    hipLaunchKernelGGL((syrks_kernel<32, 1, V - 10, false>), dim3(G), dim3(NTHR), 0, stream, s);
-  } else if constexpr (V == 22) {
-    hipLaunchKernelGGL((syrks_kernel<32, 2, 2, false>), dim3(G), dim3(NTHR), 0, stream, s);
-  } else {
-    hipLaunchKernelGGL((syrks_kernel<16, 2, 2, false>), dim3(G), dim3(NTHR), 0, stream, s);
-  }
-#else
-  else {
-    static_assert(V % 100000 >= 30000, "the shipped library has only the half-refill ring");
-  }
-#endif
-}
 
 }  // namespace
 
@@ -1388,7 +1101,7 @@ int syrk_cus() {
 
 size_t syrk_split_workspace_bytes(int64_t n, int64_t d) {
   if (n < 1 || d < 1) return 0;
-  if (syrk_variant(d) == 163) return make_layout(n, d, syrk_cus(), 0).total;
+  if (d <= kFusedMaxD) return make_layout(n, d, syrk_cus(), 0).total;
   return make_layout(n, d, syrk_cus(), default_chunk_rows(n, d)).total;
 }
 
@@ -1402,8 +1115,7 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
   DEIG_REQUIRE(lds >= d && lds % 4 == 0, "syrk: lds must be >= d and a multiple of 4");
   DEIG_REQUIRE(X && S && aligned16(X) && aligned16(S), "syrk: X and S must be 16-byte aligned");
   const int G = syrk_cus();
-  const int variant = syrk_variant(d);
-  const bool fused = variant == 163;
+  const bool fused = d <= kFusedMaxD;
   // Largest chunk (multiple of 32 rows, <= n rounded up) that fits the workspace.
   Layout L0 = make_layout(n, d, G, 0);
   const size_t ws_min = L0.total + (fused ? 0 : (size_t)ROWS_PAD * L0.dp * 4);
@@ -1450,7 +1162,6 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
   int64_t flush_rows = 4096;
   while (flush_rows < 16384 && (flush_rows * 2) * (flush_rows * 2) <= 128 * n) flush_rows *= 2;
 #endif
-  s.prio = 0;  // s_setprio staggering measured slower (374 vs 342 ms, r02)
   s.pace = reinterpret_cast<unsigned*>(base + L.off_pace);
   // XCD pacing every 64 K-tiles (2048 rows): config 3 L2 hit rate 0.52 -> 0.75, fabric
   // read requests halved, 345 -> 334 ms (r02, interleaved A/B in one process;
@@ -1460,14 +1171,18 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
 #else
   s.pace_kt = 64;
 #endif
-  s.xm = (int)L.xm;
-  s.rpace = kSyrkRem & 1;
-#ifndef DEIG_AB_SYRK_SUPER_ORDER
+  // Remainder rounds are paced too (r04, interleaved A/B in one process,
+  // profiles/r04za_syrk_*_ab.log, unpaced / paced: config 2 - d = 3072, all 78 tiles
+  // remainder - 26.84 / 26.13 ms; d = 4096 22.78 / 22.45; d = 5120 71.8 / 66.7; config-3
+  // shard 303.5 / 305.0, within its ~1.5 ms spread): unpaced, the blocks of a remainder
+  // round drift apart over their ~2500 K-tiles as the full phases' did.  Numbering the
+  // remainder items XCD-major (each XCD's blocks on K ranges no other XCD reads) cost
+  // more in balance (nseg a multiple of 8) than it saved in L2 misses (27.15, 23.37,
+  // 72.6 ms at the same shapes).
   if (G == 256 && s.nt % 8 == 0)
     hipLaunchKernelGGL(tile_order_compact_kernel, dim3((unsigned)cdiv((s.nt / 8) * (s.nt / 8), 256)), dim3(256), 0,
                        stream, s.nt, reinterpret_cast<int*>(base + L.off_order));
   else
-#endif
     hipLaunchKernelGGL(tile_order_kernel,
                        dim3((unsigned)cdiv(cdiv(s.nt, SUPER_H) * cdiv(s.nt, SUPER_W), 256)), dim3(256), 0, stream,
                        s.nt, reinterpret_cast<int*>(base + L.off_order));
@@ -1490,10 +1205,10 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
     s.flush_kt = (int)(flush_rows / ROWS_PAD);
     if (s.flush_kt < 1) s.flush_kt = 1;
     if (s.pace_kt > 0) DEIG_HIP_CHECK(hipMemsetAsync(s.pace, 0, 9 * 128, stream));
-    hipLaunchKernelGGL((syrks_kernel<16, 2, 2, true>), dim3(G), dim3(NTHR), 0, stream, s);
+    hipLaunchKernelGGL(syrks_kernel, dim3(G), dim3(NTHR), 0, stream, s);
     DEIG_HIP_CHECK(hipGetLastError());
     if (s.R > 0) {
-      hipLaunchKernelGGL(syrks_reduce_kernel<16>, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
+      hipLaunchKernelGGL(syrks_reduce_kernel, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
       DEIG_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(diag_corr_kernel, dim3((unsigned)cdiv(d, 64)), dim3(256), 0, stream, corr,
@@ -1503,10 +1218,8 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
   }
   for (int64_t r0 = 0, c = 0; r0 < n; r0 += chunk, ++c) {
     const int64_t rows = (n - r0) < chunk ? (n - r0) : chunk;
-    const int64_t nk32 = cdiv(rows, ROWS_PAD);  // 32-row blocks (zero-padded)
-    const int64_t noct = nk32 * (ROWS_PAD / 8);
-    const int kt_steps = (variant >= 13 && variant <= 15) ? 1 : 2;  // k-steps per K-tile
-    const int64_t nk = nk32 * (ROWS_PAD / 16) / kt_steps;
+    const int64_t nk = cdiv(rows, ROWS_PAD);  // K-tiles = 32-row blocks (zero-padded)
+    const int64_t noct = nk * (ROWS_PAD / 8);
     int64_t yb = cdiv(noct, 4);
     if (yb > L.yb_max) yb = L.yb_max;
     hipLaunchKernelGGL(split_kernel, dim3((unsigned)(L.dp / 256), (unsigned)yb), dim3(256), 0,
@@ -1515,16 +1228,12 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
     s.NK = nk;
     s.nseg = (int)L.nseg;
     s.beta = (c > 0 || accumulate) ? 1 : 0;
-    s.flush_kt = (int)(flush_rows / (16 * kt_steps));
-    const bool mf16 = variant >= 100;  // 162, 163, 1PQR0, 2000R: 16x16x32 slabs
+    s.flush_kt = (int)(flush_rows / ROWS_PAD);
     if (s.pace_kt > 0) DEIG_HIP_CHECK(hipMemsetAsync(s.pace, 0, 9 * 128, stream));
-    if (variant != 163) launch_split_pass_kernel<kSyrkLarge == 163 ? 162 : kSyrkLarge>(G, stream, s);
+    hipLaunchKernelGGL(syrks_h_kernel, dim3(G), dim3(NTHR), 0, stream, s);
     DEIG_HIP_CHECK(hipGetLastError());
     if (s.R > 0) {
-      if (mf16)
-        hipLaunchKernelGGL(syrks_reduce_kernel<16>, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
-      else
-        hipLaunchKernelGGL(syrks_reduce_kernel<32>, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
+      hipLaunchKernelGGL(syrks_reduce_kernel, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
       DEIG_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(diag_corr_kernel, dim3((unsigned)cdiv(d, 64)), dim3(256), 0, stream, corr,

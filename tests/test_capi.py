@@ -139,7 +139,7 @@ def test_library_reads_no_environment():
     import shutil
     import subprocess
     csrc = os.path.join(os.path.dirname(_lib.HERE), "distributed_eigenspaces_amd", "csrc")
-    for root, _, files in os.walk(csrc):  # csrc/ab/ holds the A/B-only sources
+    for root, _, files in os.walk(csrc):
         for f in files:
             assert "getenv" not in open(os.path.join(root, f)).read(), os.path.join(root, f)
     nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"

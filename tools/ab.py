@@ -1,6 +1,6 @@
 """One A/B harness for libdeig measurement builds (measurement tooling: the shipped
 library reads no environment and has no knobs; variants differ only by -D macros the
-sources test, e.g. DEIG_AB_OJA_LATE_TRANSPOSE, DEIG_AB_SYRK_VARIANT, DEIG_AB_SWEEP_DEPTH).
+sources test, e.g. DEIG_AB_SYRK_PACE, DEIG_AB_BATCH_GROUPS, DEIG_AB_SWEEP_DEPTH).
 
 Builds are interleaved in ONE process on the same inputs (the same binary runs 3-4 %
 apart across boxes, so only interleaved runs compare), each reporting its median time
