@@ -270,9 +270,11 @@ int skinny_launch(bool trans_a, const float* A, int64_t lda, const float* B, int
     DEIG_REQUIRE(M % 4 == 0 && lda >= M, "skinny(T): M %% 4 and lda >= M required");
   else
     DEIG_REQUIRE(K % 4 == 0 && lda >= K, "skinny(N): K %% 4 and lda >= K required");
+  DEIG_REQUIRE(A && B && C, "skinny: A, B, C must not be NULL");
   const int ks = choose_ks(M, K);
   const size_t need = ks > 1 ? (size_t)ks * M * N * sizeof(float) : 0;
   if (slab_bytes < need) return fail(DEIG_EWORKSPACE, "skinny: slab %zu < %zu", slab_bytes, need);
+  if (need && !slab) return fail(DEIG_EWORKSPACE, "skinny: NULL slab, %zu bytes needed", need);
   const int NB = (int)(N / 16);
   int rc = trans_a ? launch_t<true>(NB, A, lda, B, ldb, C, ldc, M, K, alpha, beta, slab, ks, stream, pbt)
                    : launch_t<false>(NB, A, lda, B, ldb, C, ldc, M, K, alpha, beta, slab, ks,

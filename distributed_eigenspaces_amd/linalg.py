@@ -91,11 +91,13 @@ def require_device_tensor(t, name: str = "input", keep_f64: bool = False) -> tor
 
 
 def _rowmajor_4(t: torch.Tensor, name: str) -> torch.Tensor:
-    """2-D row-major view with unit column stride, row stride % 4 == 0, 16-B aligned."""
+    """2-D row-major view with unit column stride, columns and row stride % 4 == 0, 16-B
+    aligned; anything else (a 37-column slice of a 40-column tensor included) is copied
+    into a zero-padded tensor, so what lies behind the columns never enters."""
     if t.dim() != 2:
         raise ValueError(f"{name} must be 2-D, got shape {tuple(t.shape)}")
     ok = (t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1]
-          and t.data_ptr() % 16 == 0)
+          and t.shape[1] % 4 == 0 and t.data_ptr() % 16 == 0)
     if ok:
         return t
     d = t.shape[1]
@@ -103,6 +105,14 @@ def _rowmajor_4(t: torch.Tensor, name: str) -> torch.Tensor:
     out = torch.zeros((t.shape[0], dp), dtype=torch.float32, device=t.device)
     out[:, :d] = t
     return out
+
+
+def _ld(t: torch.Tensor, dim: int, extent: int) -> int:
+    """Leading dimension of ``t`` along ``dim`` as the library wants it (>= extent, the
+    length of one row or column).  For a dimension of size 1 torch reports an arbitrary
+    stride (``(1, 1)`` for a ``(d, 1)`` tensor, whatever its layout): there is no second
+    row or column, so the extent itself describes the same memory."""
+    return int(extent) if t.shape[dim] == 1 else t.stride(dim)
 
 
 def default_subspace(d: int, k: int) -> int:
@@ -325,7 +335,7 @@ def _warm(q0, d, device):
     if q.shape[0] != d:
         raise ValueError(f"q0 must have {d} rows")
     q = q.t().contiguous().t()  # column-major
-    return q, q.shape[1], q.stride(1)
+    return q, q.shape[1], _ld(q, 1, d)
 
 
 def _solver_matrix(S: torch.Tensor) -> torch.Tensor:
@@ -642,7 +652,7 @@ def oja_step(Xb: torch.Tensor, V: torch.Tensor, eta: float) -> torch.Tensor:
         nbytes = L.deig_oja_workspace(b, d, k)
         ws = _workspace(Xb.device, nbytes)
         rc = L.deig_oja_step_f32(Xb.data_ptr(), b, d, Xb.stride(0), ctypes.c_float(eta),
-                                 V.data_ptr(), k, V.stride(1), ws.data_ptr(), nbytes,
+                                 V.data_ptr(), k, _ld(V, 1, d), ws.data_ptr(), nbytes,
                                  _stream(Xb.device))
     _lib.check(rc, "deig_oja_step_f32")
     oja_check(Xb.device, b, d, k)
@@ -690,7 +700,7 @@ def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
         nbytes = L.deig_oja_workspace(b, d, k)
         ws = _workspace(X.device, nbytes)
         rc = L.deig_oja_steps_ex(X.data_ptr(), nb, b, d, X.stride(0), ctypes.c_float(eta),
-                                 V.data_ptr(), k, V.stride(1), int(orth_every),
+                                 V.data_ptr(), k, _ld(V, 1, d), int(orth_every),
                                  _lib.OJA_ALGOS[algo], ws.data_ptr(), nbytes, _stream(X.device))
     _lib.check(rc, "deig_oja_steps_ex")
     if check:
@@ -809,8 +819,12 @@ def project(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     """Y = X W  (NB:345 ``X @ matrix_w``): X (n, d) row-major, W (d, k) any layout."""
     X = _rowmajor_4(require_device_tensor(X, "project"), "X")
     W = require_device_tensor(W, "matrix_w")
+    if W.dim() != 2:
+        raise ValueError(f"matrix_w must be 2-D (d, k), got shape {tuple(W.shape)}")
     n, dp = X.shape
     d, k = W.shape
+    if not 1 <= k <= 256:
+        raise ValueError(f"k={k} out of range [1, 256]")
     if d > dp or (dp != d and dp != (d + 3) // 4 * 4):
         raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
     if dp != d:
@@ -823,8 +837,8 @@ def project(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(X.device):
         nbytes = L.deig_project_workspace(n, dp, k)
         ws = _workspace(X.device, nbytes)
-        rc = L.deig_project_f32(X.data_ptr(), n, dp, X.stride(0), W.data_ptr(), k, W.stride(1),
-                                Y.data_ptr(), Y.stride(0), ws.data_ptr(), nbytes,
+        rc = L.deig_project_f32(X.data_ptr(), n, dp, _ld(X, 0, dp), W.data_ptr(), k,
+                                _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k), ws.data_ptr(), nbytes,
                                 _stream(X.device))
     _lib.check(rc, "deig_project_f32")
     return Y
@@ -836,22 +850,36 @@ def gemm_skinny(A: torch.Tensor, B: torch.Tensor, trans_a: bool, alpha: float = 
     """C = alpha * op(A) @ B + beta * C on the solvers' skinny fp32-MFMA kernel.
 
     trans_a: A is (K, M) and op(A) = A^T; else A is (M, K).  B is (K, N) with
-    N % 16 == 0 and N <= 256.  All row-major float32 on one device."""
+    N % 16 == 0 and N <= 256.  All row-major float32 on one device: A and B with
+    another column stride are copied; C (written in place, returned) must be an
+    (M, N) float32 tensor on A's device with unit column stride."""
     A = require_device_tensor(A, "A")
     B = require_device_tensor(B, "B")
+    if A.dim() != 2 or B.dim() != 2:
+        raise ValueError(f"A and B must be 2-D, got {tuple(A.shape)} and {tuple(B.shape)}")
+    if B.device != A.device:
+        raise ValueError("A and B must live on one device")
     K, M = (A.shape if trans_a else (A.shape[1], A.shape[0]))
     N = B.shape[1]
     if B.shape[0] != K:
         raise ValueError("inner dimensions differ")
+    if A.stride(1) != 1:
+        A = A.contiguous()
+    if B.stride(1) != 1:
+        B = B.contiguous()
     if C is None:
         C = torch.zeros((M, N), dtype=torch.float32, device=A.device)
+    elif not isinstance(C, torch.Tensor) or C.dim() != 2 or tuple(C.shape) != (M, N) \
+            or C.dtype != torch.float32 or C.device != A.device or C.stride(1) != 1:
+        raise ValueError(f"C must be a ({M}, {N}) float32 tensor on A's device with unit "
+                         "column stride")
     L = _lib.lib()
     with torch.cuda.device(A.device):
         nbytes = L.deig_gemm_skinny_workspace(M, N, K)
         ws = _workspace(A.device, nbytes)
-        rc = L.deig_gemm_skinny_f32(int(trans_a), A.data_ptr(), A.stride(0), B.data_ptr(),
-                                    B.stride(0), C.data_ptr(), C.stride(0), M, N, K,
-                                    ctypes.c_float(alpha), ctypes.c_float(beta), ws.data_ptr(),
+        rc = L.deig_gemm_skinny_f32(int(trans_a), A.data_ptr(), _ld(A, 0, A.shape[1]),
+                                    B.data_ptr(), _ld(B, 0, N), C.data_ptr(), _ld(C, 0, N), M, N,
+                                    K, ctypes.c_float(alpha), ctypes.c_float(beta), ws.data_ptr(),
                                     nbytes, _stream(A.device))
     _lib.check(rc, "deig_gemm_skinny_f32")
     return C

@@ -417,7 +417,10 @@ size_t deig_project_workspace(int64_t n, int64_t d, int k);
  * C[M x N] = alpha * op(A) * B + beta * C  on fp32 MFMA (16x16x4), N % 16 == 0, N <= 256.
  * trans_a != 0: A is K x M row-major (lda), op(A) = A^T  (S*Q with S symmetric, Gram)
  * trans_a == 0: A is M x K row-major (lda)              (Wt*Q, Xb*V)
- * B is K x N row-major (ldb), C is M x N row-major (ldc).  Deterministic split-K. */
+ * B is K x N row-major (ldb), C is M x N row-major (ldc).  Deterministic split-K.
+ * A and B 16-byte aligned, lda % 4 == ldb % 4 == 0; trans_a: M % 4 == 0, else K % 4 == 0.
+ * beta == 0: C is not read.  NULL A, B or C: DEIG_EINVAL; a workspace below the query
+ * (or NULL where the query is not 0): DEIG_EWORKSPACE; both before any GPU work. */
 int deig_gemm_skinny_f32(int trans_a, const float* A, int64_t lda, const float* B, int64_t ldb,
                          float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, float alpha,
                          float beta, void* ws, size_t ws_bytes, void* stream);

@@ -75,6 +75,84 @@ def test_invalid_arguments_rejected_before_any_gpu_work():
         _lib.check(_lib.DEIG_EINVAL, "x")
     with pytest.raises(_lib.DeigError):
         _lib.check(_lib.DEIG_EHIP, "x")
+    # NULL operands everywhere: each call breaks exactly one shape rule, which is
+    # reported before anything looks at a pointer
+    for args, word in SKINNY_BAD:
+        assert _skinny_null(*args) == _lib.DEIG_EINVAL, args
+        assert word in _lib.last_error(), (args, _lib.last_error())
+    for args in PROJECT_BAD:
+        assert _project_null(*args) == _lib.DEIG_EINVAL, args
+        assert "project" in _lib.last_error(), (args, _lib.last_error())
+
+
+def _skinny_null(trans, lda, ldb, ldc, M, N, K, A=None, B=None, C=None):
+    return _lib.lib().deig_gemm_skinny_f32(trans, A, lda, B, ldb, C, ldc, M, N, K,
+                                           ctypes.c_float(1.0), ctypes.c_float(0.0), None, 0, None)
+
+
+def _project_null(n, d, ldx, k, ldw, ldy, X=None, W=None, Y=None):
+    return _lib.lib().deig_project_f32(X, n, d, ldx, W, k, ldw, Y, ldy, None, 0, None)
+
+
+# (trans, lda, ldb, ldc, M, N, K), a word of the message
+SKINNY_BAD = [
+    ((0, 64, 32, 32, 64, 24, 64), "N=24"),
+    ((0, 64, 32, 32, 64, 0, 64), "N=0"),
+    ((0, 64, 272, 272, 64, 272, 64), "N=272"),
+    ((0, 64, 32, 32, 0, 32, 64), "empty"),
+    ((0, 64, 32, 32, 64, 32, 0), "empty"),
+    ((1, 64, 32, 32, 0, 32, 64), "empty"),
+    ((0, 66, 32, 32, 64, 32, 64), "leading dims"),   # lda % 4
+    ((1, 66, 32, 32, 64, 32, 64), "leading dims"),
+    ((0, 64, 30, 32, 64, 32, 64), "leading dims"),   # ldb % 4
+    ((0, 64, 28, 32, 64, 32, 64), "leading dims"),   # ldb < N
+    ((0, 64, 32, 31, 64, 32, 64), "leading dims"),   # ldc < N
+    ((1, 64, 32, 32, 62, 32, 64), "skinny(T)"),      # M % 4
+    ((1, 64, 32, 32, 68, 32, 8), "skinny(T)"),       # lda < M
+    ((0, 64, 32, 32, 64, 32, 62), "skinny(N)"),      # K % 4
+    ((0, 64, 32, 32, 8, 32, 68), "skinny(N)"),       # lda < K
+]
+
+# (n, d, ldx, k, ldw, ldy)
+PROJECT_BAD = [
+    (10, 6, 8, 2, 8, 2),        # d % 4
+    (10, 0, 8, 2, 8, 2),        # d = 0
+    (0, 8, 8, 2, 8, 2),         # n = 0
+    (10, 8, 8, 0, 8, 2),        # k = 0
+    (10, 8, 8, 257, 8, 257),    # k > 256
+    (10, 8, 8, 2, 7, 2),        # ldw < d
+    (10, 8, 8, 2, 8, 1),        # ldy < k
+    (10, 8, 10, 2, 8, 2),       # ldx % 4
+    (10, 8, 4, 2, 8, 2),        # ldx < d
+]
+
+
+def test_null_operands_rejected():
+    """Every shape rule holds and an operand is NULL: DEIG_EINVAL from the host-side
+    checks.  Nothing may be launched, so this runs only where there is no GPU to launch
+    on (host buffers stand in for the operands that are not NULL)."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    raw = (ctypes.c_float * (3 * 64 * 64 + 8))()
+    base = (ctypes.addressof(raw) + 15) // 16 * 16
+    ptr = [base + i * 64 * 64 * 4 for i in range(3)]
+    shape = (64, 32, 32, 64, 32, 64)  # lda, ldb, ldc, M, N, K: valid for both forms
+    for trans in (0, 1):
+        for null in [(0,), (1,), (2,), (0, 1, 2)]:
+            ops = [None if i in null else ptr[i] for i in range(3)]
+            assert _skinny_null(trans, *shape, A=ops[0], B=ops[1], C=ops[2]) == _lib.DEIG_EINVAL
+            assert "NULL" in _lib.last_error(), (trans, null, _lib.last_error())
+    # a split-K shape whose workspace claims a size and is NULL
+    assert _lib.lib().deig_gemm_skinny_workspace(4, 32, 520) > 0
+    rc = _lib.lib().deig_gemm_skinny_f32(0, ptr[0], 520, ptr[1], 32, ptr[2], 32, 4, 32, 520,
+                                         ctypes.c_float(1.0), ctypes.c_float(0.0), None, 1 << 20,
+                                         None)
+    assert rc == _lib.DEIG_EWORKSPACE and "NULL" in _lib.last_error()
+    for null in [(0,), (1,), (2,), (0, 1, 2)]:
+        ops = [None if i in null else ptr[i] for i in range(3)]
+        assert _project_null(10, 8, 8, 2, 8, 2, X=ops[0], W=ops[1], Y=ops[2]) == _lib.DEIG_EINVAL
+        assert "project" in _lib.last_error(), (null, _lib.last_error())
 
 
 def test_no_cpu_fallback():
