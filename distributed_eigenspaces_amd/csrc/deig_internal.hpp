@@ -18,6 +18,7 @@ typedef __attribute__((address_space(3))) void lds_void;
 // ---------------------------------------------------------------- error handling
 void set_error(const char* fmt, ...);
 int fail(int code, const char* fmt, ...);
+const char* last_error();  // the calling thread's message (deig_last_error)
 
 #define DEIG_HIP_CHECK(expr)                                                          \
   do {                                                                                \
@@ -92,7 +93,7 @@ int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode
 //   trans_a = true : A is K x M row-major (op(A) = A^T)
 //   trans_a = false: A is M x K row-major
 //   B is K x N row-major; N % 16 == 0, N <= 256.
-// Launches that cover several problems of one shape (solve_batch): problem i's
+// Launches that cover several problems of one shape (solver.hip Lockstep): problem i's
 // workspace buffers sit off[i] bytes after problem 0's (off[0] = 0; the solver
 // workspaces are equally carved slices of one allocation); outputs outside the
 // workspaces are per problem.
@@ -153,7 +154,7 @@ struct SweepStep {
   int write_y;              // 1: also store Y = alpha S Q (split-K sums); 0: Y is dead (the
                             // solver's intermediate sweeps: only the basis step reads it)
 };
-// Several problems of the same d, p and mode in one launch per kernel (solve_batch):
+// Several problems of the same d, p and mode in one launch per kernel (solver.hip Lockstep):
 // problem i's Q, Y, workspace and step buffers sit off[i] bytes after problem 0's
 // (off[0] = 0); the fused step's scalars are per problem, its pointers and next_mode
 // problem 0's.
@@ -188,11 +189,9 @@ struct RRBuffers {
 // Start basis (Q0's k0 columns, then pseudo-random ones); rows >= valid zero (< 0: none).
 int rr_init_launch(float* Z, int64_t d, int p, const float* Q0, int k0, int64_t ldq0,
                    uint64_t seed, hipStream_t stream, int64_t valid = -1);
-// max_jsweeps caps the Jacobi sweeps of the small eigenproblem (30 = converge);
-// jrel: a pair is rotated while |h_ab| > jrel sqrt(|h_aa h_bb|) (2e-7: to rounding).
-int rr_small_launch(const RRBuffers& b, int p, hipStream_t stream, int max_jsweeps = 30,
-                    float jrel = 2e-7f);
 // n independent small solves in launches of up to kRRBatch workgroups (one each).
+// max_jsweeps[i] caps the Jacobi sweeps of problem i's small eigenproblem (30 = converge);
+// jrel: a pair is rotated while |h_ab| > jrel sqrt(|h_aa h_bb|) (2e-7: to rounding).
 constexpr int kRRBatch = 16;
 int rr_small_batch_launch(const RRBuffers* const* bs, const int* max_jsweeps, int n, int p,
                           hipStream_t stream, float jrel = 2e-7f);
@@ -201,9 +200,8 @@ int rr_power_launch(const RRBuffers& b, int64_t d, int p, float tau, hipStream_t
 // One scaled Chebyshev filter degree on Z = [X_j | A X_j] with T = X_{j-1} (d x p).
 int cheb_step_launch(const RRBuffers& b, float* T, int64_t d, int p, float thr, float alpha,
                      float cc, float gamma, hipStream_t stream);
-int rr_update_launch(const RRBuffers& b, int64_t d, int p, int k, float* V, int64_t ldv,
-                     float* evals, hipStream_t stream);
-// The same for batch.n problems (RRBuffers of problem i at off[i]; V / evals per problem).
+// Ritz vectors, residuals and the next basis for batch.n problems (RRBuffers of problem
+// i at off[i]; V / evals per problem).
 int rr_update_batch_launch(const RRBuffers& b0, int64_t d, int p, int k, int64_t ldv,
                            const ProbBatch& batch, hipStream_t stream);
 // Columns 0..kc-1 of V (col-major, ldv) made orthogonal to columns kc..kc+r-1, normalised.
@@ -242,5 +240,70 @@ int procrustes_launch(const float* Wt, int64_t d, int64_t mk, int64_t ldw, int k
 size_t subspace_dist_workspace_bytes(int64_t d, int k);
 int subspace_dist_launch(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t d, int k,
                          float* out, void* ws, size_t ws_bytes, hipStream_t st);
+
+// ---------------------------------------------------------------- Eigensolver driver (solver.hip)
+struct Opts {
+  int sweep_algo = DEIG_SWEEP_BF16X6;
+  int rr_every = 0;
+  bool cheb = true;
+  float cheb_above = -1.f;  // < 0: per solve (Solver::iter_begin)
+  bool deflate = true;
+  bool deflate_early = true;
+  int jcap_sweeps = -1;
+  float jcap_above = -1.f;
+  float fast_until = 1e-3f;
+  float round_until = 1e-4f;
+  float half_until = 1e-2f;
+  bool debug = false;
+};
+Opts make_opts(const deig_solver_opts* o);  // nullptr: the defaults
+
+struct Operator {
+  bool implicit;
+  const void* S;  // explicit: d x d row-major (lds), element type stype
+  int stype;
+  int64_t lds;
+  const float* Wt;  // implicit: scale * Wt^T Wt
+  int64_t mk, ldw;
+  float scale;
+  // applied on top of the base operator (image: folded in by sweep_prepare;
+  // plain products: applied after each product): + shift I - Vd diag(lamd) Vd^T
+  double shift;
+  const float* Vd;
+  int64_t ldvd;
+  const float* lamd;
+  int r;
+};
+
+int default_subspace(int64_t d, int k);
+// Is an explicit d x d S staged (copied into a zero-padded image in the workspace)?
+// Then it needs only its element alignment, else 16 bytes and lds % 4 == 0.
+bool solver_stages(int64_t d, int k, int p);
+// Workspace of one problem (mk: rows of an implicit operator's Wt; stype: an explicit S's).
+size_t solver_workspace_bytes(int64_t d, int k, int p, bool implicit, int64_t mk, const Opts& o,
+                              int stype);
+
+// One problem of a solve: its operator, warm start (k0 columns of Q0, column-major,
+// ldq0; k0 = 0: none) and outputs (V d x k column-major, evals ascending).
+struct SolveProblem {
+  Operator op;
+  const float* Q0;
+  int k0;
+  int64_t ldq0;
+  float* V;
+  float* evals;
+};
+// Top-k eigenpairs of W problems of one shape, advanced in lockstep (W = 1: a single
+// solve).  Problem i's workspace is the ws_each bytes at ws + i * ws_each.  Returns a
+// mid-solve error, else the first problem's outcome that is not DEIG_OK (with its
+// message); sweeps_out / resid_out / status_out (each optional, W entries) get every
+// problem's own outcome.  Nothing is written when a problem cannot be set up.
+int solve_lockstep(int W, const SolveProblem* pr, int64_t d, int k, int p, int max_sweeps,
+                   float tol, int64_t ldv, int* sweeps_out, float* resid_out, int* status_out,
+                   const Opts& o, void* ws, size_t ws_each, hipStream_t st);
+
+// deig_shutdown: does the pool of pinned status blocks hold any? / free the idle ones.
+bool status_pool_empty();
+void status_pool_drain();
 
 }  // namespace deig

@@ -32,7 +32,7 @@ namespace {
 
 constexpr int kMaxK = 128;       // widest basis (2 x 128 x 132 floats of LDS)
 constexpr int kMaxJSweeps = 30;  // the Jacobi loop always ends
-constexpr float kJRel = 2e-7f;   // rotate while |g_p . g_q| > kJRel ||g_p|| ||g_q|| (rr_small_launch's jrel)
+constexpr float kJRel = 2e-7f;   // rotate while |g_p . g_q| > kJRel ||g_p|| ||g_q|| (rr_small_batch_launch's jrel)
 constexpr float kDropRel = 1e-5f;     // polar: singular values below this * c_max give no term
 constexpr float kDropRelInv = 1e-6f;  // inverse square root: the same guard (C = Vbar^T Vbar)
 

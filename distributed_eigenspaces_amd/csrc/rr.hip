@@ -1,10 +1,10 @@
 // Rayleigh-Ritz step of the block subspace-iteration eigensolver that replaces
 // LAPACK dsyevr in Node.top_k_eigenvectors (distributed.py:22-29).
 //
-// Per sweep the driver (capi.hip) keeps Z = [Q | Y] (d x 2p, row-major) with
+// Per sweep the driver (solver.hip) keeps Z = [Q | Y] (d x 2p, row-major) with
 // Y = A Q, forms the Gram C = Z^T Z (skinny GEMM) and then:
 //
-//  rr_small2_kernel / rr_small2_batch_kernel (ONE workgroup per problem, p <= 128,
+//  rr_small2_kernel (ONE workgroup per problem, p <= 128,
 //  everything in LDS; the body, rr_small2_body, documents the steps):
 //    M = Q^T Q, H = Q^T Y, G = Y^T Y taken from C;
 //    D = diag(M)^-1/2;  D M D = L L^T (blocked Cholesky, pivots floored);
@@ -38,7 +38,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 }
 
 // Start basis: Q0's k0 columns, then pseudo-random columns.  Rows >= valid are zero
-// (the zero padding of a staged S, capi.hip: its directions then never enter the
+// (the zero padding of a staged S, solver.hip: its directions then never enter the
 // basis - S Q, the shift, deflation and Rayleigh-Ritz all keep zero rows zero).
 __global__ __launch_bounds__(256) void rr_init_kernel(float* __restrict__ Z, int64_t d, int p,
                                                       const float* __restrict__ Q0, int k0,
@@ -639,33 +639,27 @@ __device__ __forceinline__ void rr_small2_body(const float* __restrict__ Cg, int
   stamp(8);
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void rr_small2_kernel(const float* __restrict__ Cg, int p,
-                                                       float* __restrict__ Wout,
-                                                       float* __restrict__ lam_out,
-                                                       float* __restrict__ cs_out,
-                                                       float* __restrict__ qs_out,
-                                                       int* __restrict__ info, int max_jsweeps,
-                                                       float jrel) {
-  rr_small2_body<NT>(Cg, p, Wout, lam_out, cs_out, qs_out, info, max_jsweeps, jrel);
-}
-
 // Up to kRRBatch independent small solves in one launch, one workgroup each (the
-// batched worker solves: W problems' Rayleigh-Ritz steps side by side on W CUs).
+// batched worker solves: W problems' Rayleigh-Ritz steps side by side on W CUs; a
+// single solve is a launch of one).
+// One record per problem, one 64-byte line of the kernel-argument segment each: a
+// workgroup's scalar loads of its arguments then miss once, as separate kernel
+// parameters would (with one array per field they touched eight lines, which cost
+// every small solve 1.0 us, 0.4 - 0.8 % of a single solve:
+// profiles/r08a_lockstep_driver_ab.log).
 struct RRBatchArgs {
-  const float* C[kRRBatch];
-  float* W[kRRBatch];
-  float* lam[kRRBatch];
-  float* cs[kRRBatch];
-  float* qs[kRRBatch];
-  int* info[kRRBatch];
-  int max_jsweeps[kRRBatch];
+  struct alignas(64) Prob {
+    const float* C;
+    float *W, *lam, *cs, *qs;
+    int* info;
+    int max_jsweeps;
+  } prob[kRRBatch];
 };
 
 template <int NT>
-__global__ __launch_bounds__(NT) void rr_small2_batch_kernel(RRBatchArgs a, int p, float jrel) {
-  const int i = blockIdx.x;
-  rr_small2_body<NT>(a.C[i], p, a.W[i], a.lam[i], a.cs[i], a.qs[i], a.info[i], a.max_jsweeps[i], jrel);
+__global__ __launch_bounds__(NT) void rr_small2_kernel(RRBatchArgs a, int p, float jrel) {
+  const RRBatchArgs::Prob& q = a.prob[blockIdx.x];
+  rr_small2_body<NT>(q.C, p, q.W, q.lam, q.cs, q.qs, q.info, q.max_jsweeps, jrel);
 }
 
 // blockIdx.y: the problem of a batched launch (its buffers at pbt.off, V = pbt.V).
@@ -887,7 +881,7 @@ __global__ __launch_bounds__(256) void rr_power_kernel(float* __restrict__ Z, in
 }
 
 // One degree of the scaled Chebyshev filter between two Rayleigh-Ritz steps
-// (Zhou & Saad's scaled three-term recurrence; capi.hip plans alpha / cc / gamma
+// (Zhou & Saad's scaled three-term recurrence; solver.hip plans alpha / cc / gamma
 // from the last RR's Ritz values).  Z = [X_j | A X_j] (ld 2p), T = X_{j-1} (ld p):
 //   X_{j+1} = alpha (A X_j - cc X_j) - gamma X_{j-1};  T <- X_j;  Z_q <- X_{j+1}
 // for the active columns (Ritz value >= thr); the others keep X_0 (like the weak
@@ -920,7 +914,7 @@ __global__ __launch_bounds__(256) void cheb_step_kernel(float* __restrict__ Z,
   *zq = xn;
 }
 
-// After a deflated stage or block (capi.hip): V_j <- normalize(V_j - V_D V_D^T V_j)
+// After a deflated stage or block (solver.hip): V_j <- normalize(V_j - V_D V_D^T V_j)
 // for the kc columns of the stage against the r locked ones (V_D = columns kc ..
 // kc + r - 1).  The deflated operator S - lam_1 v^ v^T keeps a coupling
 // lam_1 (v_1 d^T + d v_1^T) from the small error d = v^ - v_1, which tilts each
@@ -1295,22 +1289,11 @@ int rr_init_launch(float* Z, int64_t d, int p, const float* Q0, int k0, int64_t 
   return DEIG_OK;
 }
 
-int rr_small_launch(const RRBuffers& b, int p, hipStream_t stream, int max_jsweeps, float jrel) {
-  DEIG_REQUIRE(p >= 16 && p <= 128 && p % 16 == 0, "rr_small: p=%d out of range", p);
-  static const hipError_t attr2 = hipFuncSetAttribute(
-      (const void*)rr_small2_kernel<RT2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rr_small2_shm(128));
-  DEIG_HIP_CHECK(attr2);
-  hipLaunchKernelGGL(rr_small2_kernel<RT2>, dim3(1), dim3(RT2), rr_small2_shm(p), stream, b.C, p, b.W, b.lam,
-                     b.cs, b.qs, b.info, max_jsweeps, jrel);
-  DEIG_HIP_CHECK(hipGetLastError());
-  return DEIG_OK;
-}
-
 int rr_small_batch_launch(const RRBuffers* const* bs, const int* max_jsweeps, int n, int p,
                           hipStream_t stream, float jrel) {
   DEIG_REQUIRE(p >= 16 && p <= 128 && p % 16 == 0, "rr_small: p=%d out of range", p);
   static const hipError_t attr2 = hipFuncSetAttribute(
-      (const void*)rr_small2_batch_kernel<RT2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (const void*)rr_small2_kernel<RT2>, hipFuncAttributeMaxDynamicSharedMemorySize,
       (int)rr_small2_shm(128));
   DEIG_HIP_CHECK(attr2);
   for (int i0 = 0; i0 < n; i0 += kRRBatch) {
@@ -1318,15 +1301,9 @@ int rr_small_batch_launch(const RRBuffers* const* bs, const int* max_jsweeps, in
     RRBatchArgs a{};
     for (int i = 0; i < m; ++i) {
       const RRBuffers& b = *bs[i0 + i];
-      a.C[i] = b.C;
-      a.W[i] = b.W;
-      a.lam[i] = b.lam;
-      a.cs[i] = b.cs;
-      a.qs[i] = b.qs;
-      a.info[i] = b.info;
-      a.max_jsweeps[i] = max_jsweeps[i0 + i];
+      a.prob[i] = {b.C, b.W, b.lam, b.cs, b.qs, b.info, max_jsweeps[i0 + i]};
     }
-    hipLaunchKernelGGL(rr_small2_batch_kernel<RT2>, dim3(m), dim3(RT2), rr_small2_shm(p), stream, a, p, jrel);
+    hipLaunchKernelGGL(rr_small2_kernel<RT2>, dim3(m), dim3(RT2), rr_small2_shm(p), stream, a, p, jrel);
     DEIG_HIP_CHECK(hipGetLastError());
   }
   return DEIG_OK;
@@ -1428,14 +1405,6 @@ int unshift_launch(float* evals, int k, double shift, hipStream_t stream) {
 }
 
 int rr_update_blocks(int64_t d) { return (int)cdiv(d, UR); }
-
-int rr_update_launch(const RRBuffers& b, int64_t d, int p, int k, float* V, int64_t ldv,
-                     float* evals, hipStream_t stream) {
-  ProbBatch one = one_problem();
-  one.V[0] = V;
-  one.evals[0] = evals;
-  return rr_update_batch_launch(b, d, p, k, ldv, one, stream);
-}
 
 int rr_update_batch_launch(const RRBuffers& b, int64_t d, int p, int k, int64_t ldv,
                            const ProbBatch& pbt, hipStream_t stream) {

@@ -177,7 +177,7 @@ size_t si_bytes(int64_t d) { return (size_t)si_rows(d) * si_groups(d) * 32 * 4; 
 // to the dominant eigenvalues' (for a float64 S - the reference's dtype - this is
 // what keeps the small eigenvectors at float64 parity; an fp32 chain of fmas
 // would round every intermediate at |S_ij|).  shift: the solver's indefinite-input
-// shift (capi.hip), 0 otherwise.
+// shift (solver.hip), 0 otherwise.
 template <typename T>
 __global__ __launch_bounds__(256) void sweep_prepare_kernel(const T* __restrict__ S, int64_t lds,
                                                             int64_t d, int64_t ng, int64_t nunits,
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256) void sweep_prepare_kernel(const T* __restrict_
 // PRE: SI is the two-piece image (sweep_prepare_kernel's SH: h | m per half slot)
 // and the products are the three of SP = 2 - the early-sweep mode, no split.
 // per / sb (every sweep kernel): one launch may cover sb.n problems of the same shape
-// (the batched worker solves, capi.hip solve_batch): logical blocks [i per, (i + 1) per)
+// (the batched worker solves, solver.hip Lockstep): logical blocks [i per, (i + 1) per)
 // are problem i's, and every pointer of problem i is problem 0's plus sb.off[i] bytes
 // (the solver workspaces are equally carved slices of one allocation).  One problem:
 // per = the grid, sb.n = 1.

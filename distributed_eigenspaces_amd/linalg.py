@@ -29,7 +29,7 @@ __all__ = [
 
 DEFAULT_TOL = 1e-6
 DEFAULT_MAX_SWEEPS = 300
-MAX_P = 128  # widest subspace of one solver block (kMaxP in csrc/capi.hip); k > 128
+MAX_P = 128  # widest subspace of one solver block (kMaxP in csrc/solver.hip); k > 128
              # is solved in locked blocks of p - 16 pairs
 
 

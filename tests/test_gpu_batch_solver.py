@@ -39,8 +39,8 @@ def test_batch_equals_separate_solves(dtype, cuda):
 
 
 def test_batch_two_stream_groups_equal_separate_solves(cuda):
-    """d >= 2048: the batch runs as two interleaved groups on two streams (capi.hip
-    solve_batch, r06); an odd count (groups of 2 and 1) with one dominant-mean problem
+    """d >= 2048: the batch runs as two interleaved groups on two streams (solver.hip
+    Lockstep, r06); an odd count (groups of 2 and 1) with one dominant-mean problem
     (deflation path): still bit-identical to separate solves, and everything is
     ordered on the caller's stream when the call returns."""
     import distributed_eigenspaces_amd as de
@@ -61,6 +61,44 @@ def test_batch_two_stream_groups_equal_separate_solves(cuda):
         assert torch.equal(a.V, b.V)
         assert torch.equal(a.evals, b.evals)
         assert torch.equal(c, (a.V * 1.0).sum())
+
+
+def test_batch_fp32_sweep_equals_separate_solves(cuda):
+    """The fp32 sweep has no image, so no batched sweep launch: every problem of the
+    batch must still get its own product Y = S Q each sweep (d = 128, k = 8, p = 16;
+    one problem with a dominant mean, so the deflation redo runs through the
+    plain-product operator too).  Bit-identical to separate solves, all converged."""
+    import distributed_eigenspaces_amd as de
+    from distributed_eigenspaces_amd import _lib
+    d, k = 128, 8
+    o = _lib.solver_opts(sweep_algo=_lib.DEIG_SWEEP_FP32)
+    Ss = [_spiked_cov(d, k, 2048, 20 + 5 * i, cuda, mean=(3.0 if i == 1 else 0.0)).float()
+          for i in range(3)]
+    single = [de.topk_eigh(S, k, opts=o) for S in Ss]
+    batch = de.topk_eigh_batch(Ss, k, opts=o)
+    torch.cuda.synchronize()
+    for a, b in zip(single, batch):
+        assert a.converged and b.converged
+        assert a.sweeps == b.sweeps
+        assert torch.equal(a.V, b.V)
+        assert torch.equal(a.evals, b.evals)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_batch_of_one_equals_single_solve(dtype, cuda):
+    """The two C entry points report the same outputs for one problem: bit-equal V and
+    eigenvalues, equal sweeps, residual and convergence flag."""
+    import distributed_eigenspaces_amd as de
+    d, k = 128, 8
+    S = _spiked_cov(d, k, 2048, 31, cuda).to(dtype)
+    a = de.topk_eigh(S, k)
+    b = de.topk_eigh_batch([S], k)[0]
+    torch.cuda.synchronize()
+    assert torch.equal(a.V, b.V)
+    assert torch.equal(a.evals, b.evals)
+    assert a.sweeps == b.sweeps
+    assert a.resid == b.resid
+    assert a.converged == b.converged
 
 
 def test_batch_c1_shape_vs_oracle(cuda):

@@ -6,7 +6,7 @@ flattened in float64 (distributed.py:170-173), with an UNCENTERED covariance
 (:59-70): the mean direction's eigenvalue is ~1e4 x the k-th one.  Two things make
 the GPU path match eigh there to 1e-4: the exact integer covariance of the bytes
 (csrc/syrk_u8.hip; an fp32 accumulation's noise alone would move the basis by
-~3e-4) and the solver's deflation of the dominant pair (csrc/capi.hip, stage 2;
+~3e-4) and the solver's deflation of the dominant pair (csrc/solver.hip, stage 2;
 fp32 products S q otherwise lose the small eigenvalues' digits to cancellation).
 
 CIFAR itself is not in the reference snapshot (.MISSING_LARGE_BLOBS), so the bytes

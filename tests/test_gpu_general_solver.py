@@ -1,6 +1,6 @@
 """The GPU top_k_eigenvectors is as general as the reference's (distributed.py:22-29:
 ``scipy.linalg.eigh(matrix, eigvals=(N-k, N-1))`` - any symmetric matrix, any
-1 <= k <= N): k > 128 (block locking, csrc/capi.hip solve) and indefinite input
+1 <= k <= N): k > 128 (block locking, csrc/solver.hip SolveSM) and indefinite input
 (detected from the Ritz values, solved as S + sigma I), for explicit float32 /
 float64 matrices and for the implicit projector average (server, k > 128).
 

@@ -3,7 +3,7 @@ subspace iteration converges slowly, and the no-silent-stall contract.
 
 The reference's top-k is LAPACK ?syevr (distributed.py:29, ``eigh(matrix,
 eigvals=(N-k, N-1))``), exact at any gap; the GPU solver is subspace iteration
-with a Chebyshev filter between Rayleigh-Ritz steps (csrc/capi.hip cheb_plan).
+with a Chebyshev filter between Rayleigh-Ritz steps (csrc/solver.hip cheb_plan).
 Bars where the problem allows them: ||P - P_ref||_F <= 1e-4 and eigenvalues 1e-5
 relative against float64 eigh of the same fp32 matrix; where it does not (gap
 0.99, a residual floor at the fp32 level is ~1e-2 of the gap), the solver must

@@ -1,4 +1,4 @@
-"""NumPy fp32 emulation of the solver's outer loop (capi.hip solve) with the
+"""NumPy fp32 emulation of the solver's outer loop (solver.hip) with the
 Chebyshev filter between Rayleigh-Ritz steps, for choosing its parameters.
 
 usage: python tools/emulate_cheb.py

@@ -1,4 +1,4 @@
-"""NumPy emulation of the GPU solver's algorithm (capi.hip solve + rr.hip) for debugging."""
+"""NumPy emulation of the GPU solver's algorithm (solver.hip + rr.hip) for debugging."""
 import numpy as np
 
 
