@@ -8,6 +8,9 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
   * projavg_topk   - implicit projector-average solve         (distributed.py:126-130, NB:306)
   * procrustes_average - Procrustes-aligned basis average (one-pass aggregator, no eigensolve)
   * subspace_distance / projector_distance - residual-form sin Theta on the device
+  * column_sums / sigma_hat_centered - opt-in centred covariance about a pooled mean
+  * pca_transform  - fused centred scores + per-row energy and reconstruction error;
+                     pca.PCA wraps the centred estimator in sklearn's conventions
   * oja_step(s)    - mini-batch Oja (online variant, config 4); streaming.StreamingOja
                      adds the periodic all-gather / server solve / broadcast
 
@@ -15,8 +18,10 @@ Drop-in modules: ``distributed`` (Node / SlaveNode / MasterNode / run_* / main),
 ``my_threading`` (Slave) and ``notebook`` (make_batches, top_k_eigenvectors,
 compute_segma_hat, online loop).
 """
-from .linalg import (EigResult, default_subspace, oja_step, oja_steps, procrustes_average,  # noqa: F401
-                     projavg_topk, projector_distance, sigma_hat, stack_bases, subspace_distance,
-                     sym_apply, sym_power, topk_eigh, topk_eigh_batch)
+from .linalg import (EigResult, column_sums, default_subspace, oja_step, oja_steps,  # noqa: F401
+                     pca_transform, procrustes_average, projavg_topk, projector_distance, sigma_hat,
+                     sigma_hat_centered, stack_bases, subspace_distance, sym_apply, sym_power,
+                     topk_eigh, topk_eigh_batch)
+from .pca import PCA  # noqa: F401
 
 __version__ = "0.1.0"

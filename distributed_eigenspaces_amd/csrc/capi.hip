@@ -160,6 +160,26 @@ int deig_syrk_shift(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
                            (hipStream_t)stream);
 }
 
+size_t deig_colsum_workspace(int64_t n, int64_t d) { return colsum_workspace_bytes(n, d); }
+
+int deig_colsum(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double* sums, void* ws,
+                size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return colsum_launch(X, xtype, n, d, ldx, sums, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t deig_syrk_centered_workspace(int64_t n, int64_t d, int xtype) {
+  return syrk_centered_workspace_bytes(n, d, xtype);
+}
+
+int deig_syrk_centered(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                       const double* center, double alpha, double* S64, int64_t lds64, float* S,
+                       int64_t lds, double* mean_out, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return syrk_centered_launch(X, xtype, n, d, ldx, center, alpha, S64, lds64, S, lds, mean_out, ws,
+                              ws_bytes, (hipStream_t)stream);
+}
+
 size_t deig_syrk_u8_workspace(int64_t n, int64_t d, int mode) {
   return syrk_u8_workspace_bytes(n, d, mode);
 }
@@ -425,6 +445,18 @@ int deig_project_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const fl
                      int64_t ldw, float* Y, int64_t ldy, void* ws, size_t ws_bytes, void* stream) {
   g_err[0] = 0;
   return project_launch(X, n, d, ldx, W, k, ldw, Y, ldy, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t deig_pca_transform_workspace(int64_t n, int64_t d, int k) {
+  return pca_transform_workspace_bytes(n, d, k);
+}
+
+int deig_pca_transform_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                           const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
+                           float* energy, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return pca_transform_launch(X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws, ws_bytes,
+                              (hipStream_t)stream);
 }
 
 size_t deig_gemm_skinny_workspace(int64_t M, int64_t N, int64_t K) {

@@ -83,6 +83,17 @@ int syrk_shift_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
                       double* S64, int64_t lds64, float* S, int64_t lds, void* ws, size_t ws_bytes,
                       hipStream_t stream);
 
+// Centred covariance alpha sum_r (x_r - c)(x_r - c)^T on the same pipeline (shift.hip);
+// center = nullptr: the shard's own mean.  Column sums in double: its first pass alone.
+size_t syrk_centered_workspace_bytes(int64_t n, int64_t d, int xtype);
+int syrk_centered_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                         const double* center, double alpha, double* S64, int64_t lds64, float* S,
+                         int64_t lds, double* mean_out, void* ws, size_t ws_bytes,
+                         hipStream_t stream);
+size_t colsum_workspace_bytes(int64_t n, int64_t d);
+int colsum_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double* sums,
+                  void* ws, size_t ws_bytes, hipStream_t stream);
+
 // Exact uint8 covariance on int8 MFMA (syrk_u8.hip); mode DEIG_U8_RAW / DEIG_U8_GRAY3.
 size_t syrk_u8_workspace_bytes(int64_t n, int64_t d, int mode);
 int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double alpha,
@@ -229,6 +240,15 @@ int oja_error(const void* ws, size_t ws_bytes, int64_t b, int64_t d, int k, hipS
 size_t project_workspace_bytes(int64_t n, int64_t d, int k);
 int project_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const float* W, int k,
                    int64_t ldw, float* Y, int64_t ldy, void* ws, size_t ws_bytes, hipStream_t st);
+// Wr (d x kp row-major, kp % 16 == 0, columns >= k zero) from the column-major d x k W.
+int pack_w_launch(const float* W, int64_t ldw, int64_t d, int k, int kp, float* Wr,
+                  hipStream_t st);
+
+// Fused centred transform (pca.hip): Y = (X - 1 mean^T) W, row energies and residuals.
+size_t pca_transform_workspace_bytes(int64_t n, int64_t d, int k);
+int pca_transform_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                         const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
+                         float* energy, void* ws, size_t ws_bytes, hipStream_t st);
 
 // Procrustes-aligned basis average and residual-form subspace distance (procrustes.hip).
 // Both validate their arguments (DEIG_EINVAL) before any GPU work; the workspace

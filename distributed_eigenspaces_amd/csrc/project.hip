@@ -44,6 +44,16 @@ ProjWs carve_proj(void* ws, size_t cap, int64_t n, int64_t d, int kp, bool direc
 
 }  // namespace
 
+// Wr (d x kp row-major, columns >= k zero) from the column-major d x k W; also the
+// W image of the fused centred transform (pca.hip).
+int pack_w_launch(const float* W, int64_t ldw, int64_t d, int k, int kp, float* Wr,
+                  hipStream_t st) {
+  hipLaunchKernelGGL(w_to_rowpad, dim3((unsigned)cdiv(d * kp, 256)), dim3(256), 0, st, W, ldw, d,
+                     k, kp, Wr);
+  DEIG_HIP_CHECK(hipGetLastError());
+  return DEIG_OK;
+}
+
 size_t project_workspace_bytes(int64_t n, int64_t d, int k) {
   const int kp = (int)cdiv(k, 16) * 16;
   size_t total = 0;
@@ -63,11 +73,10 @@ int project_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const floa
   ProjWs o = carve_proj(ws, ws_bytes, n, d, kp, direct, &total);
   if (!ws || total > ws_bytes)
     return fail(DEIG_EWORKSPACE, "project: workspace %zu < %zu", ws_bytes, total);
-  hipLaunchKernelGGL(w_to_rowpad, dim3((unsigned)cdiv(d * kp, 256)), dim3(256), 0, st, W, ldw, d,
-                     k, kp, o.Wr);
-  DEIG_HIP_CHECK(hipGetLastError());
-  int rc = skinny_launch(false, X, ldx, o.Wr, kp, direct ? Y : o.T, direct ? ldy : kp, n, kp, d,
-                         1.f, 0.f, o.slab, o.slab_bytes, st);
+  int rc = pack_w_launch(W, ldw, d, k, kp, o.Wr, st);
+  if (rc) return rc;
+  rc = skinny_launch(false, X, ldx, o.Wr, kp, direct ? Y : o.T, direct ? ldy : kp, n, kp, d, 1.f,
+                     0.f, o.slab, o.slab_bytes, st);
   if (rc) return rc;
   if (!direct) {
     hipLaunchKernelGGL(crop_rows, dim3((unsigned)cdiv(n * k, 256)), dim3(256), 0, st, o.T, n, k,

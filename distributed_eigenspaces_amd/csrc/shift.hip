@@ -17,10 +17,17 @@
 // covariance SYRK of C (split3 / fp32 by n, syrk_split.hip / syrk.hip) into an fp32
 // image Sc = alpha C^T C; shift_finalize: S64 = Sc + alpha (s mu^T + mu s^T + n mu mu^T)
 // written from symmetric expressions (bit-exact symmetry), and optionally S = fl32(S64).
+//
+// Centred covariance (deig_syrk_centered): the same pipeline with the finalize pass taking
+// delta = mu - c in place of mu,  alpha sum_r (x_r - c)(x_r - c)^T =
+//   alpha [ C^T C + s delta^T + delta s^T + n delta delta^T ]     (exact identity; mu is still
+// the shard's own mean, so the SYRK keeps its rounding on the centred scale whatever c is).
+// c = 0 is deig_syrk_shift (delta = mu: the same launches on the same values, the same bits);
+// c = NULL is the shard's own mean (delta = 0).  The column sums of the first pass are also
+// an entry point of their own (deig_colsum).
 #include "deig_internal.hpp"
 
 namespace deig {
-namespace {
 
 constexpr int CS_YB = 128;  // row groups of the column passes
 
@@ -52,6 +59,8 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const double* __restrict
   out[f] = scale * s;
 }
 
+namespace {
+
 template <typename T>
 __global__ __launch_bounds__(256) void center_kernel(const T* __restrict__ X, int64_t n,
                                                      int64_t ldx, int64_t d, int64_t dp,
@@ -73,7 +82,7 @@ __global__ __launch_bounds__(256) void center_kernel(const T* __restrict__ X, in
 
 __global__ __launch_bounds__(256) void shift_finalize_kernel(const float* __restrict__ Sc,
                                                              int64_t ldc, int64_t d,
-                                                             const double* __restrict__ mu,
+                                                             const double* __restrict__ delta,
                                                              const double* __restrict__ sv,
                                                              double n, double alpha,
                                                              double* __restrict__ S64,
@@ -86,7 +95,7 @@ __global__ __launch_bounds__(256) void shift_finalize_kernel(const float* __rest
   // No contraction: fused into fma(sv_i, mu_j, mu_i sv_j) the cross term would round
   // differently for (j, i) - r03's float64 Sigma was not bit-symmetric
   // (tests/test_gpu_integration_stub.py).
-  const double mi = mu[i], mj = mu[j];
+  const double mi = delta[i], mj = delta[j];
   double cross;
   {
 #pragma clang fp contract(off)
@@ -97,14 +106,27 @@ __global__ __launch_bounds__(256) void shift_finalize_kernel(const float* __rest
   if (S) S[i * lds + j] = (float)v;
 }
 
+// delta = mu - c (c = NULL: the shard's own mean, delta = 0); mean_out = mu (optional)
+__global__ __launch_bounds__(256) void delta_kernel(const double* __restrict__ mu,
+                                                    const double* __restrict__ c, int64_t d,
+                                                    double* __restrict__ delta,
+                                                    double* __restrict__ mean_out) {
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= d) return;
+  const double m = mu[f];
+  delta[f] = c ? m - c[f] : 0.0;
+  if (mean_out) mean_out[f] = m;
+}
+
 struct ShiftLayout {
   int64_t dp;
   int yb;
   int algo;
-  size_t off_part, off_mu, off_s, off_c, off_sc, off_syrk, syrk_bytes, total;
+  size_t off_part, off_mu, off_s, off_c, off_sc, off_syrk, syrk_bytes, off_delta, total;
 };
 
-ShiftLayout shift_layout(int64_t n, int64_t d) {
+// centered: room for delta behind the deig_syrk_shift layout (whose offsets and size stay)
+ShiftLayout shift_layout(int64_t n, int64_t d, bool centered = false) {
   ShiftLayout L;
   L.dp = cdiv(d, 4) * 4;
   L.yb = (int)(n < CS_YB ? (n > 0 ? n : 1) : CS_YB);
@@ -124,13 +146,17 @@ ShiftLayout shift_layout(int64_t n, int64_t d) {
   off = align_up(off + (size_t)L.dp * L.dp * sizeof(float), 256);
   L.off_syrk = off;
   L.total = L.off_syrk + L.syrk_bytes;
+  L.off_delta = align_up(L.total, 256);
+  if (centered) L.total = L.off_delta + (size_t)L.dp * sizeof(double);
   return L;
 }
 
+// centered = false: c = 0 (deig_syrk_shift; center and mean_out unused)
 template <typename T>
 int shift_run(const T* X, int64_t n, int64_t d, int64_t ldx, double alpha, double* S64,
               int64_t lds64, float* S, int64_t lds, char* base, const ShiftLayout& L,
-              hipStream_t st) {
+              hipStream_t st, bool centered = false, const double* center = nullptr,
+              double* mean_out = nullptr) {
   double* part = reinterpret_cast<double*>(base + L.off_part);
   double* mu = reinterpret_cast<double*>(base + L.off_mu);
   double* sv = reinterpret_cast<double*>(base + L.off_s);
@@ -152,8 +178,16 @@ int shift_run(const T* X, int64_t n, int64_t d, int64_t ldx, double alpha, doubl
                ? syrk_split_launch(C, n, L.dp, L.dp, (float)alpha, Sc, L.dp, sws, L.syrk_bytes, st)
                : syrk_launch(C, n, L.dp, L.dp, (float)alpha, Sc, L.dp, sws, L.syrk_bytes, st);
   if (rc) return rc;
+  const double* delta = mu;
+  if (centered) {
+    double* dl = reinterpret_cast<double*>(base + L.off_delta);
+    hipLaunchKernelGGL(delta_kernel, dim3((unsigned)cdiv(d, 256)), dim3(256), 0, st, mu, center, d,
+                       dl, mean_out);
+    DEIG_HIP_CHECK(hipGetLastError());
+    delta = dl;
+  }
   hipLaunchKernelGGL(shift_finalize_kernel, dim3((unsigned)cdiv(d * d, 256)), dim3(256), 0, st, Sc,
-                     L.dp, d, mu, sv, (double)n, alpha, S64, lds64, S, lds);
+                     L.dp, d, delta, sv, (double)n, alpha, S64, lds64, S, lds);
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
 }
@@ -184,6 +218,70 @@ int syrk_shift_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
   if (xtype == DEIG_F64)
     return shift_run(static_cast<const double*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st);
   return shift_run(static_cast<const float*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st);
+}
+
+size_t syrk_centered_workspace_bytes(int64_t n, int64_t d, int xtype) {
+  (void)xtype;
+  if (n < 1 || d < 1) return 0;
+  return shift_layout(n, d, true).total;
+}
+
+int syrk_centered_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                         const double* center, double alpha, double* S64, int64_t lds64, float* S,
+                         int64_t lds, double* mean_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_F64, "syrk_centered: unknown element type %d", xtype);
+  DEIG_REQUIRE(n >= 1 && d >= 1, "syrk_centered: need n >= 1, d >= 1");
+  DEIG_REQUIRE(ldx >= d, "syrk_centered: ldx must be >= d");
+  DEIG_REQUIRE(S64 || S, "syrk_centered: need S64 and/or S");
+  DEIG_REQUIRE(!S64 || lds64 >= d, "syrk_centered: lds64 must be >= d");
+  DEIG_REQUIRE(!S || lds >= d, "syrk_centered: lds must be >= d");
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % (xtype == DEIG_F64 ? 8 : 4)) == 0,
+               "syrk_centered: X must be aligned to its element size");
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % 8 == 0 &&
+                   reinterpret_cast<uintptr_t>(mean_out) % 8 == 0,
+               "syrk_centered: center and mean_out must be 8-byte aligned");
+  const ShiftLayout L = shift_layout(n, d, true);
+  if (!ws || ws_bytes < L.total)
+    return fail(DEIG_EWORKSPACE, "syrk_centered: workspace %zu bytes < required %zu", ws_bytes, L.total);
+  char* base = static_cast<char*>(ws);
+  if (xtype == DEIG_F64)
+    return shift_run(static_cast<const double*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st,
+                     true, center, mean_out);
+  return shift_run(static_cast<const float*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st,
+                   true, center, mean_out);
+}
+
+size_t colsum_workspace_bytes(int64_t n, int64_t d) {
+  if (n < 1 || d < 1) return 0;
+  const int64_t yb = n < CS_YB ? n : CS_YB;
+  return align_up((size_t)yb * d * sizeof(double), 256);
+}
+
+int colsum_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double* sums,
+                  void* ws, size_t ws_bytes, hipStream_t st) {
+  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_F64, "colsum: unknown element type %d", xtype);
+  DEIG_REQUIRE(n >= 1 && d >= 1, "colsum: need n >= 1, d >= 1");
+  DEIG_REQUIRE(ldx >= d, "colsum: ldx must be >= d");
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % (xtype == DEIG_F64 ? 8 : 4)) == 0,
+               "colsum: X must be aligned to its element size");
+  DEIG_REQUIRE(sums && reinterpret_cast<uintptr_t>(sums) % 8 == 0, "colsum: sums must be 8-byte aligned");
+  const size_t need = colsum_workspace_bytes(n, d);
+  if (!ws || ws_bytes < need)
+    return fail(DEIG_EWORKSPACE, "colsum: workspace %zu bytes < required %zu", ws_bytes, need);
+  const int yb = (int)(n < CS_YB ? n : CS_YB);
+  double* part = static_cast<double*>(ws);
+  const dim3 g((unsigned)cdiv(d, 256), (unsigned)yb);
+  if (xtype == DEIG_F64)
+    hipLaunchKernelGGL(colsum_kernel<double>, g, dim3(256), 0, st, static_cast<const double*>(X), n,
+                       ldx, d, part);
+  else
+    hipLaunchKernelGGL(colsum_kernel<float>, g, dim3(256), 0, st, static_cast<const float*>(X), n,
+                       ldx, d, part);
+  DEIG_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)cdiv(d, 256)), dim3(256), 0, st, part, yb, d,
+                     1.0, sums);
+  DEIG_HIP_CHECK(hipGetLastError());
+  return DEIG_OK;
 }
 
 }  // namespace deig

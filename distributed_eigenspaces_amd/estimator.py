@@ -15,6 +15,12 @@ projectors (:126-130).  Here:
   ``aggregate="procrustes"`` the server is the Procrustes-aligned average instead
   (``linalg.procrustes_average``: no eigensolve, columns follow V_1's).
 
+``center=True`` (opt-in; the reference never centres) estimates the eigenspace of the
+CENTRED covariance: one more collective before the workers run - an all-reduce of the
+float64 column sums and row counts into the pooled mean (``global_mean``) - and every
+logical worker's covariance is taken about that pooled mean
+(``linalg.sigma_hat_centered``), so the shards estimate the same matrix.
+
 The collective layer only uses ``torch.distributed`` with tensors on the rank's
 device, so it runs on ``gloo`` with CPU tensors too (multi-process tests); the
 per-worker compute is injectable for those tests and defaults to the GPU ops.
@@ -30,7 +36,7 @@ import torch.distributed as dist
 from . import linalg
 
 __all__ = ["shard_ranges", "rank_shards", "EstimatorResult", "DistributedEigenspaceEstimator",
-           "gather_bases"]
+           "gather_bases", "global_mean"]
 
 
 AGGREGATES = ("projector", "procrustes")
@@ -73,6 +79,19 @@ def gather_bases(Wt_local: torch.Tensor, group=None) -> torch.Tensor:
     return out.to(Wt_local.device)
 
 
+def global_mean(sums: torch.Tensor, n_rows: int, group=None) -> torch.Tensor:
+    """Pooled column mean of all ranks' rows: ONE ``all_reduce(SUM)`` of the float64 vector
+    [sums, n_rows] (this rank's column sums and row count), then sums / n.  Returns a (d,)
+    float64 tensor on ``sums``' device, the same on every rank."""
+    v = torch.cat([sums.detach().to(torch.float64).reshape(-1),
+                   torch.tensor([float(n_rows)], dtype=torch.float64, device=sums.device)])
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        buf = comm_tensor(v, group)  # v itself under RCCL, a host copy under gloo
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+        v = buf.to(sums.device)
+    return v[:-1] / v[-1]
+
+
 @dataclass
 class EstimatorResult:
     evals: torch.Tensor | None     # (k,) ascending, server rank only
@@ -82,6 +101,7 @@ class EstimatorResult:
     sweeps_worker: list
     sweeps_server: int
     cosines: torch.Tensor | None = None  # aggregate="procrustes": (m, k) cosines basis i / V_1
+    mean: torch.Tensor | None = None     # center=True: the pooled column mean, (d,) float64
 
 
 def _batch_accepts(solver_kw: dict) -> bool:
@@ -92,8 +112,16 @@ def _batch_accepts(solver_kw: dict) -> bool:
     return all(key in params and key not in ("Ss", "k") for key in solver_kw)
 
 
-def _gpu_worker(x: torch.Tensor, k: int, **kw):
-    S = linalg.sigma_hat(x)
+def _covariance(x: torch.Tensor, center=None) -> torch.Tensor:
+    """A logical worker's covariance: the reference's uncentred one, or (center=True fits)
+    the covariance about the pooled mean."""
+    if center is None:
+        return linalg.sigma_hat(x)
+    return linalg.sigma_hat_centered(x, center=center)
+
+
+def _gpu_worker(x: torch.Tensor, k: int, center=None, **kw):
+    S = _covariance(x, center)
     r = linalg.topk_eigh(S, k, check_finite=False, **kw)
     return r.V, r.evals, r.sweeps
 
@@ -101,7 +129,8 @@ def _gpu_worker(x: torch.Tensor, k: int, **kw):
 class DistributedEigenspaceEstimator:
     def __init__(self, k: int, workers_per_rank: int = 1, server_rank: int = 0, group=None,
                  worker_fn=None, solver_kw=None, concurrent_workers: bool = False,
-                 batched_workers: bool = True, aggregate: str = "projector"):
+                 batched_workers: bool = True, aggregate: str = "projector",
+                 center: bool = False):
         if aggregate not in AGGREGATES:
             raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
         # "projector" (default, the reference's server): top-k of the projector average;
@@ -122,38 +151,52 @@ class DistributedEigenspaceEstimator:
         self.group = group
         self.worker_fn = worker_fn or _gpu_worker
         self.solver_kw = dict(solver_kw or {})
+        # center (opt-in): the eigenspace of the covariance about the pooled mean of all
+        # ranks' rows; the default stays the reference's uncentred second moment.
+        self.center = bool(center)
 
     def _rank_world(self):
         if dist.is_available() and dist.is_initialized():
             return dist.get_rank(self.group), dist.get_world_size(self.group)
         return 0, 1
 
-    def local_bases(self, X_local: torch.Tensor):
-        """Run this rank's logical workers on contiguous pieces of X_local."""
+    def pooled_mean(self, X_local: torch.Tensor) -> torch.Tensor:
+        """The mean of the rows that the workers of all ranks use: this rank's
+        wpr * (n // wpr) rows (the remainder is dropped, as the shards drop it)."""
+        used = self.wpr * (X_local.shape[0] // self.wpr)
+        rows = X_local[:used]
+        # host tensors: the gloo rehearsal with an injected worker
+        sums = linalg.column_sums(rows) if rows.is_cuda else rows.to(torch.float64).sum(dim=0)
+        return global_mean(sums, used, self.group)
+
+    def local_bases(self, X_local: torch.Tensor, center: torch.Tensor | None = None):
+        """Run this rank's logical workers on contiguous pieces of X_local (center: the
+        pooled mean of a centred fit, None = uncentred)."""
         parts = shard_ranges(X_local.shape[0], self.wpr)
+        ckw = {} if center is None else {"center": center}
         if self.concurrent and len(parts) > 1 and X_local.is_cuda:
-            return self._local_bases_concurrent(X_local, parts)
+            return self._local_bases_concurrent(X_local, parts, center)
         if self.batched and len(parts) > 1 and X_local.is_cuda and _batch_accepts(self.solver_kw):
-            Ss = [linalg.sigma_hat(X_local[lo:hi]) for lo, hi in parts]
+            Ss = [_covariance(X_local[lo:hi], center) for lo, hi in parts]
             rs = linalg.topk_eigh_batch(Ss, self.k, check_finite=False, **self.solver_kw)
             return (torch.cat([r.V.t() for r in rs], dim=0).contiguous(), [r.evals for r in rs],
                     [r.sweeps for r in rs])
         rows, evs, sw = [], [], []
         for lo, hi in parts:
-            V, ev, s = self.worker_fn(X_local[lo:hi], self.k, **self.solver_kw)
+            V, ev, s = self.worker_fn(X_local[lo:hi], self.k, **ckw, **self.solver_kw)
             rows.append(V.t())  # k x d view of the column-major basis
             evs.append(ev)
             sw.append(s)
         return torch.cat(rows, dim=0).contiguous(), evs, sw
 
-    def _local_bases_concurrent(self, X_local: torch.Tensor, parts):
+    def _local_bases_concurrent(self, X_local: torch.Tensor, parts, center=None):
         from .my_threading import Slave
         dev = X_local.device
         main = torch.cuda.current_stream(dev)
         slaves = []
         try:
             for lo, hi in parts:
-                S = linalg.sigma_hat(X_local[lo:hi])
+                S = _covariance(X_local[lo:hi], center)
                 ev = torch.cuda.Event()
                 ev.record(main)
                 st = torch.cuda.Stream(dev)
@@ -195,13 +238,14 @@ class DistributedEigenspaceEstimator:
 
     def fit(self, X_local: torch.Tensor) -> EstimatorResult:
         rank, world = self._rank_world()
-        Wt_local, evs, sw = self.local_bases(X_local)
+        mean = self.pooled_mean(X_local) if self.center else None
+        Wt_local, evs, sw = self.local_bases(X_local, mean)
         Wt = gather_bases(Wt_local, self.group)
         m = world * self.wpr
         if rank == self.server_rank:
             if self.aggregator == "procrustes":
                 pr = linalg.procrustes_average(Wt, self.k)
-                return EstimatorResult(None, pr.V, Wt, evs, sw, 0, cosines=pr.cosines)
+                return EstimatorResult(None, pr.V, Wt, evs, sw, 0, cosines=pr.cosines, mean=mean)
             r = self.server(Wt, m)
-            return EstimatorResult(r.evals, r.V, Wt, evs, sw, r.sweeps)
-        return EstimatorResult(None, None, Wt, evs, sw, 0)
+            return EstimatorResult(r.evals, r.V, Wt, evs, sw, r.sweeps, mean=mean)
+        return EstimatorResult(None, None, Wt, evs, sw, 0, mean=mean)

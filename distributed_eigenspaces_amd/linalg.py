@@ -25,6 +25,7 @@ __all__ = [
     "EigResult", "require_device_tensor", "project", "stack_bases", "gemm_skinny",
     "oja_steps", "oja_check", "sym_apply", "sym_power", "sigma_hat_u8", "sigma_hat_shift",
     "procrustes_average", "subspace_distance", "projector_distance", "ProcrustesResult",
+    "column_sums", "sigma_hat_centered", "pca_transform",
 ]
 
 DEFAULT_TOL = 1e-6
@@ -231,6 +232,84 @@ def sigma_hat_shift(x: torch.Tensor, alpha: float | None = None,
         out.copy_(S)
         return out
     return S
+
+
+def _float_samples(x, name: str) -> torch.Tensor:
+    """(n, d) float32 / float64 samples on the device with unit column stride."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.to(torch.float64)
+    x = require_device_tensor(x, name, keep_f64=True)
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2-D (n, d), got {tuple(x.shape)}")
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return x
+
+
+def column_sums(x: torch.Tensor) -> torch.Tensor:
+    """sums[j] = sum_r x[r, j] in double (include/deig.h deig_colsum): a (d,) float64
+    tensor, summed in a fixed order (deterministic).  x: (n, d) float32 / float64.  The
+    pooled mean of a multi-GPU centred fit is the all-reduce of these over the row count
+    (``estimator.global_mean``)."""
+    x = _float_samples(x, "column_sums")
+    n, d = x.shape
+    sums = torch.zeros(d, dtype=torch.float64, device=x.device)
+    if n == 0 or d == 0:
+        return sums
+    xtype = _lib.DEIG_F64 if x.dtype == torch.float64 else _lib.DEIG_F32
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        nbytes = L.deig_colsum_workspace(n, d)
+        ws = _workspace(x.device, nbytes)
+        rc = L.deig_colsum(x.data_ptr(), xtype, n, d, _ld(x, 0, d), sums.data_ptr(), ws.data_ptr(),
+                           nbytes, _stream(x.device))
+    _lib.check(rc, "deig_colsum")
+    return sums
+
+
+def sigma_hat_centered(x: torch.Tensor, center: torch.Tensor | None = None,
+                       alpha: float | None = None, dtype: torch.dtype | None = None,
+                       return_mean: bool = False):
+    """Centred covariance alpha * sum_r (x_r - c)(x_r - c)^T with alpha = 1/n by default
+    (include/deig.h deig_syrk_centered).  Opt-in: ``sigma_hat`` stays the reference's
+    uncentred second moment.  center: (d,) float64 (the pooled mean of a multi-shard fit,
+    so that the shards' covariances add up to the pooled one), None = this shard's own
+    mean.  The SYRK runs on fl32(x - own mean) whatever the centre; the centre enters
+    through rank-one terms in double.  Returns a (d, d) tensor of ``dtype`` (float64 by
+    default), bit-exactly symmetric; with ``return_mean`` also the shard's own mean
+    ((d,) float64)."""
+    x = _float_samples(x, "sigma_hat_centered")
+    dtype = dtype or torch.float64
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype must be torch.float32 or torch.float64")
+    n, d = x.shape
+    if n == 0:
+        S = torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
+        return (S, torch.full((d,), float("nan"), dtype=torch.float64, device=x.device)) \
+            if return_mean else S
+    c = None
+    if center is not None:
+        c = torch.as_tensor(center).to(device=x.device, dtype=torch.float64).contiguous()
+        if c.shape != (d,):
+            raise ValueError(f"center must have shape ({d},), got {tuple(c.shape)}")
+    a = (1.0 / n) if alpha is None else float(alpha)
+    xtype = _lib.DEIG_F64 if x.dtype == torch.float64 else _lib.DEIG_F32
+    S = torch.empty((d, d), dtype=dtype, device=x.device)
+    mean = torch.empty(d, dtype=torch.float64, device=x.device) if return_mean else None
+    f64 = dtype == torch.float64
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        nbytes = L.deig_syrk_centered_workspace(n, d, xtype)
+        ws = _workspace(x.device, nbytes)
+        rc = L.deig_syrk_centered(x.data_ptr(), xtype, n, d, _ld(x, 0, d),
+                                  c.data_ptr() if c is not None else None, ctypes.c_double(a),
+                                  S.data_ptr() if f64 else None, d, None if f64 else S.data_ptr(), d,
+                                  mean.data_ptr() if mean is not None else None, ws.data_ptr(),
+                                  nbytes, _stream(x.device))
+    _lib.check(rc, "deig_syrk_centered")
+    return (S, mean) if return_mean else S
 
 
 def sigma_hat_u8(x: torch.Tensor, mode: str = "auto", alpha: float | None = None,
@@ -842,6 +921,69 @@ def project(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
                                 _stream(X.device))
     _lib.check(rc, "deig_project_f32")
     return Y
+
+
+def pca_transform(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = None, *,
+                  residual: bool = False, energy: bool = False):
+    """Y = (X - mean) W in one pass over X (include/deig.h deig_pca_transform_f32), and from
+    the same pass, on request, ``energy`` (||x_i - mean||^2 per row) and ``residual``
+    (max(0, energy_i - ||y_i||^2): for an orthonormal W the squared reconstruction error,
+    accurate to a multiple of eps * energy_i, not of eps * residual_i).
+
+    X (n, d) row-major, W (d, k) any layout with k <= 256, mean (d,) or None (no
+    centring).  The mean is subtracted in double before the product.  float64 X is centred
+    in float64 here and then rounded to float32 (the kernel reads float32).  Returns Y, or
+    the tuple (Y[, residual][, energy])."""
+    if not isinstance(X, torch.Tensor):
+        X = torch.as_tensor(X)
+    mu = None
+    if mean is not None:
+        mu = torch.as_tensor(mean).to(dtype=torch.float64).reshape(-1)
+    if X.dtype == torch.float64 and mu is not None:
+        X = require_device_tensor(X, "pca_transform", keep_f64=True)
+        X, mu = (X - mu.to(X.device)).to(torch.float32), None
+    X = _rowmajor_4(require_device_tensor(X, "pca_transform"), "X")
+    W = require_device_tensor(W, "W")
+    if W.dim() != 2:
+        raise ValueError(f"W must be 2-D (d, k), got shape {tuple(W.shape)}")
+    n, dp = X.shape
+    d, k = W.shape
+    if not 1 <= k <= 256:
+        raise ValueError(f"k={k} out of range [1, 256]")
+    if d > dp or (dp != d and dp != (d + 3) // 4 * 4):
+        raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
+    if mu is not None:
+        if mu.numel() != d:
+            raise ValueError(f"mean must hold d = {d} numbers, got {mu.numel()}")
+        mu = mu.to(X.device)
+    if dp != d:  # zero columns, zero rows of W, zero mean entries
+        Wp = torch.zeros((dp, k), dtype=torch.float32, device=W.device)
+        Wp[:d] = W
+        W = Wp
+        if mu is not None:
+            mu = torch.cat([mu, torch.zeros(dp - d, dtype=torch.float64, device=mu.device)])
+    if mu is not None:
+        mu = mu.contiguous()
+    W = W.t().contiguous().t()  # column-major
+    dev = X.device
+    Y = torch.empty((n, k), dtype=torch.float32, device=dev)
+    res = torch.empty(n, dtype=torch.float32, device=dev) if residual else None
+    en = torch.empty(n, dtype=torch.float32, device=dev) if energy else None
+    if n > 0:
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            nbytes = L.deig_pca_transform_workspace(n, dp, k)
+            ws = _workspace(dev, nbytes)
+            rc = L.deig_pca_transform_f32(X.data_ptr(), n, dp, _ld(X, 0, dp),
+                                          mu.data_ptr() if mu is not None else None, W.data_ptr(),
+                                          k, _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k),
+                                          res.data_ptr() if residual else None,
+                                          en.data_ptr() if energy else None, ws.data_ptr(), nbytes,
+                                          _stream(dev))
+        _lib.check(rc, "deig_pca_transform_f32")
+    if not residual and not energy:
+        return Y
+    return tuple(t for t in (Y, res, en) if t is not None)
 
 
 # ---------------------------------------------------------------- building block

@@ -39,7 +39,8 @@ extern "C" {
 #define DEIG_EWORKSPACE (-3)
 #define DEIG_ETIMEOUT (-4) /* a resident Oja hand-off timed out (deig_oja_error) */
 
-/* Element types of float inputs (deig_syrk_shift, deig_topk_sym_ex). */
+/* Element types of float inputs (deig_syrk_shift, deig_syrk_centered, deig_colsum,
+ * deig_topk_sym_ex). */
 #define DEIG_F32 0
 #define DEIG_F64 1
 
@@ -108,6 +109,34 @@ int deig_syrk_shift(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
                     double* S64, int64_t lds64, float* S, int64_t lds, void* ws, size_t ws_bytes,
                     void* stream);
 size_t deig_syrk_shift_workspace(int64_t n, int64_t d, int xtype);
+
+/* Column sums in double: sums[j] = sum_r X[r][j] (the first pass of deig_syrk_shift as an
+ * entry point of its own; a multi-GPU centred fit all-reduces these into the pooled mean).
+ * X: n x d row-major of element type xtype (DEIG_F32 / DEIG_F64), row stride ldx, aligned
+ * to its element size; sums: d doubles on the device.  The rows are summed in a fixed
+ * order (min(n, 128) row groups, then the groups in order), so the result is
+ * deterministic.  Asynchronous on `stream`, no allocation, no synchronisation. */
+int deig_colsum(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double* sums, void* ws,
+                size_t ws_bytes, void* stream);
+size_t deig_colsum_workspace(int64_t n, int64_t d);
+
+/* Centred covariance (opt-in; the reference never centres):
+ *   S64 = alpha * sum_r (x_r - c)(x_r - c)^T,
+ * c = center (d doubles on the device; NULL = the shard's own mean mu).  It is the
+ * deig_syrk_shift pipeline with delta = mu - c where that one uses mu:
+ *   alpha [ C^T C + s delta^T + delta s^T + n delta delta^T ],  C = fl32(X - mu),
+ * so the SYRK still runs on data centred about the shard's OWN mean (its rounding stays on
+ * the centred scale for any c) and the rank-one terms are added in double from symmetric
+ * expressions.  deig_syrk_shift is exactly the case c = 0: a zero `center` gives its bits.
+ * A pooled mean as c makes the covariances of several shards add up to the pooled centred
+ * covariance (weights n_i / N with alpha = 1 / n_i).  mean_out (optional, d doubles on the
+ * device): mu.  X, S64, S as for deig_syrk_shift.  Like it, the workspace
+ * (deig_syrk_centered_workspace) holds an fp32 copy of the shard.  Asynchronous on `stream`,
+ * no allocation, no synchronisation; argument errors are DEIG_EINVAL before any GPU work. */
+int deig_syrk_centered(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                       const double* center, double alpha, double* S64, int64_t lds64, float* S,
+                       int64_t lds, double* mean_out, void* ws, size_t ws_bytes, void* stream);
+size_t deig_syrk_centered_workspace(int64_t n, int64_t d, int xtype);
 
 /* Exact covariance of uint8 samples (fused ingest):
  *   S = alpha * V^T V,  V the n x d feature matrix of
@@ -412,6 +441,30 @@ int deig_project_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const fl
                      int64_t ldw, float* Y, int64_t ldy, void* ws, size_t ws_bytes,
                      void* stream);
 size_t deig_project_workspace(int64_t n, int64_t d, int k);
+
+/* Fused centred transform, one pass over X:
+ *   Y         = (X - 1 mean^T) W            (n x k row-major, any ldy >= k, any alignment)
+ *   energy[i] = ||x_i - mean||^2            (n floats)
+ *   resid[i]  = max(0, energy[i] - ||y_i||^2)
+ * Each output may be NULL (not all three).  X: n x d row-major fp32, d % 4 == 0,
+ * ldx % 4 == 0, 16-byte aligned (as deig_project_f32); mean: d doubles on the device, NULL
+ * = no centring; W: d x k column-major (ldw, the solvers' V), 1 <= k <= 256.
+ * The mean is subtracted in double and rounded once to fp32 when X is staged, BEFORE the
+ * product (fp32 MFMA fma chain, as deig_project_f32), so Y's error is relative to
+ * |X - mean| |W| and not to |mean|.
+ * Accuracy of resid: for an orthonormal W it is the squared reconstruction error
+ * ||(x_i - mean) - W W^T (x_i - mean)||^2, formed as a difference of two fp32 norms - it
+ * is accurate to a multiple of eps * energy[i] (about (d + k) 2^-24 energy[i] at worst),
+ * NOT of eps * resid[i]: a sample that the basis reconstructs to better than ~1e-3
+ * relative has no correct digits in resid.
+ * One workgroup per 64 rows and no split over d: a small n with a large d under-fills the
+ * chip.  No atomics: repeated calls give identical bits.  Asynchronous on `stream`, no
+ * allocation, no synchronisation; argument errors are DEIG_EINVAL and a short workspace
+ * DEIG_EWORKSPACE before any GPU work.  Workspace: the packed W image. */
+int deig_pca_transform_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                           const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
+                           float* energy, void* ws, size_t ws_bytes, void* stream);
+size_t deig_pca_transform_workspace(int64_t n, int64_t d, int k);
 
 /* Building block of the solvers, exposed for direct testing / reuse:
  * C[M x N] = alpha * op(A) * B + beta * C  on fp32 MFMA (16x16x4), N % 16 == 0, N <= 256.
