@@ -11,6 +11,9 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
   * column_sums / sigma_hat_centered - opt-in centred covariance about a pooled mean
   * pca_transform  - fused centred scores + per-row energy and reconstruction error;
                      pca.PCA wraps the centred estimator in sklearn's conventions
+  * column_sums_u8 / sigma_hat_u8_centered / pca_transform_u8 - the same centred stack on
+                     uint8 samples (exact integer covariance, bytes staged by the transform;
+                     PCA(k, u8_mode="raw" | "gray"))
   * oja_step(s)    - mini-batch Oja (online variant, config 4); streaming.StreamingOja
                      adds the periodic all-gather / server solve / broadcast
 
@@ -18,9 +21,10 @@ Drop-in modules: ``distributed`` (Node / SlaveNode / MasterNode / run_* / main),
 ``my_threading`` (Slave) and ``notebook`` (make_batches, top_k_eigenvectors,
 compute_segma_hat, online loop).
 """
-from .linalg import (EigResult, column_sums, default_subspace, oja_step, oja_steps,  # noqa: F401
-                     pca_transform, procrustes_average, projavg_topk, projector_distance, sigma_hat,
-                     sigma_hat_centered, stack_bases, subspace_distance, sym_apply, sym_power,
+from .linalg import (EigResult, column_sums, column_sums_u8, default_subspace,  # noqa: F401
+                     oja_step, oja_steps, pca_transform, pca_transform_u8, procrustes_average,
+                     projavg_topk, projector_distance, sigma_hat, sigma_hat_centered,
+                     sigma_hat_u8_centered, stack_bases, subspace_distance, sym_apply, sym_power,
                      topk_eigh, topk_eigh_batch)
 from .pca import PCA  # noqa: F401
 

@@ -137,6 +137,17 @@ SIGNATURES = {
     "deig_pca_transform_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, _fp, _fp, ctypes.c_int,
                                               _c_i64, _fp, _c_i64, _fp, _fp, _vp, _c_sz, _vp]),
     "deig_pca_transform_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
+    "deig_colsum_u8": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp, _vp, _c_sz,
+                                      _vp]),
+    "deig_colsum_u8_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "deig_syrk_u8_centered": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp,
+                                             ctypes.c_double, _fp, _c_i64, _fp, _c_i64, _fp, _vp,
+                                             _c_sz, _vp]),
+    "deig_syrk_u8_centered_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
+    "deig_pca_transform_u8": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp, _fp,
+                                             ctypes.c_int, _c_i64, _fp, _c_i64, _fp, _fp, _vp,
+                                             _c_sz, _vp]),
+    "deig_pca_transform_u8_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
     "deig_projavg_topk_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_float,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_float, _fp, ctypes.c_int, _c_i64, _fp,

@@ -192,6 +192,26 @@ int deig_syrk_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, 
                         (hipStream_t)stream);
 }
 
+size_t deig_colsum_u8_workspace(int64_t n, int64_t d) { return colsum_u8_workspace_bytes(n, d); }
+
+int deig_colsum_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double* sums,
+                   void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return colsum_u8_launch(X, n, d, ldx, mode, sums, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t deig_syrk_u8_centered_workspace(int64_t n, int64_t d, int mode) {
+  return syrk_u8_centered_workspace_bytes(n, d, mode);
+}
+
+int deig_syrk_u8_centered(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                          const double* center, double alpha, float* S, int64_t lds, double* S64,
+                          int64_t lds64, double* mean_out, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return syrk_u8_centered_launch(X, n, d, ldx, mode, center, alpha, S, lds, S64, lds64, mean_out, ws,
+                                 ws_bytes, (hipStream_t)stream);
+}
+
 int deig_default_subspace(int64_t d, int k) { return default_subspace(d, k); }
 
 static size_t topk_ws(int64_t d, int k, int p, bool implicit, int64_t mk, const deig_solver_opts* o,
@@ -457,6 +477,19 @@ int deig_pca_transform_f32(const float* X, int64_t n, int64_t d, int64_t ldx, co
   g_err[0] = 0;
   return pca_transform_launch(X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws, ws_bytes,
                               (hipStream_t)stream);
+}
+
+size_t deig_pca_transform_u8_workspace(int64_t n, int64_t d, int k) {
+  return pca_transform_u8_workspace_bytes(n, d, k);
+}
+
+int deig_pca_transform_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                          const double* mean, const float* W, int k, int64_t ldw, float* Y,
+                          int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
+                          void* stream) {
+  g_err[0] = 0;
+  return pca_transform_u8_launch(X, n, d, ldx, mode, mean, W, k, ldw, Y, ldy, resid, energy, ws,
+                                 ws_bytes, (hipStream_t)stream);
 }
 
 size_t deig_gemm_skinny_workspace(int64_t M, int64_t N, int64_t K) {

@@ -99,6 +99,18 @@ size_t syrk_u8_workspace_bytes(int64_t n, int64_t d, int mode);
 int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double alpha,
                    float* S, int64_t lds, double* S64, int64_t lds64, void* ws, size_t ws_bytes,
                    hipStream_t stream);
+// Its centred form alpha sum_r (v_r - c)(v_r - c)^T (exact integer numerator, centred
+// epilogues; center = nullptr: the shard's own mean) and the integer column sums alone.
+size_t syrk_u8_centered_workspace_bytes(int64_t n, int64_t d, int mode);
+int syrk_u8_centered_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                            const double* center, double alpha, float* S, int64_t lds, double* S64,
+                            int64_t lds64, double* mean_out, void* ws, size_t ws_bytes,
+                            hipStream_t stream);
+size_t colsum_u8_workspace_bytes(int64_t n, int64_t d);
+int colsum_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double* sums,
+                     void* ws, size_t ws_bytes, hipStream_t stream);
+// The shape rules of the uint8 entry points (mode, n, d % 4, d <= dmax, ldx for the mode).
+int u8_check_shape(const char* what, int64_t n, int64_t d, int64_t ldx, int mode, int64_t dmax);
 
 // Skinny GEMM (skinny.hip):  C[M x N] = alpha * op(A) * B + beta * C
 //   trans_a = true : A is K x M row-major (op(A) = A^T)
@@ -249,6 +261,12 @@ size_t pca_transform_workspace_bytes(int64_t n, int64_t d, int k);
 int pca_transform_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
                          const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
                          float* energy, void* ws, size_t ws_bytes, hipStream_t st);
+// The same from uint8 samples, centred when the bytes are staged (pca_u8.hip).
+size_t pca_transform_u8_workspace_bytes(int64_t n, int64_t d, int k);
+int pca_transform_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                            const double* mean, const float* W, int k, int64_t ldw, float* Y,
+                            int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
+                            hipStream_t st);
 
 // Procrustes-aligned basis average and residual-form subspace distance (procrustes.hip).
 // Both validate their arguments (DEIG_EINVAL) before any GPU work; the workspace

@@ -173,7 +173,128 @@ struct U8Sched {
   double alpha;
   float* S;
   double* S64;
+  const double* e;  // CENTERED: the centre terms e_i (u8_center_kernel), fpad doubles
 };
+
+// ---- centred covariance (deig_syrk_u8_centered): S = alpha sum_r (v_r - c)(v_r - c)^T from
+// the integers the uncentred pipeline already holds.  With y the offset values (raw: x - 128,
+// gray: t = r + g + b - 384), A_ij = sum y_i y_j, Y_i = sum y_i, v = (y + off) / s
+// (off, s = 128, 1 raw; 384, 3 gray) and e_i = Y_i + off n - s n c_i = s sum_r (v_ri - c_i):
+//   s^2 sum (v_i - c_i)(v_j - c_j) = sum (y_i - Y_i/n)(y_j - Y_j/n) + e_i e_j / n
+//                                  = (n A_ij - Y_i Y_j) / n + e_i e_j / n.
+// A centred sum does not depend on the offset, so the 128 (..) / 384 (..) corrections of the
+// uncentred epilogues have no counterpart here.  n A_ij and Y_i Y_j each pass 2^63 from
+// n ~ 2^25 (|y| <= 128) while their difference, n^2 cov_ij, stays small: the numerator is
+// formed exactly in 128-bit integers (|n A|, |Y_i Y_j| <= 2^98 at n = 2^40) and rounded to
+// double once.
+// 128-bit integer to double, round to nearest even, written out (no runtime-library
+// conversion routine on the device): the top 64 bits with a sticky bit, then an exact ldexp.
+__device__ __forceinline__ double i128_to_double(__int128 v) {
+  const bool neg = v < 0;
+  const unsigned __int128 m = neg ? -(unsigned __int128)v : (unsigned __int128)v;
+  const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
+  double r;
+  if (hi == 0) {
+    r = (double)lo;
+  } else {
+    const int sh = __builtin_clzll(hi);
+    uint64_t top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+    const uint64_t rest = sh ? (lo << sh) : lo;
+    top |= (uint64_t)(rest != 0);  // sticky: 11 bits below the rounding position
+    r = ldexp((double)top, 64 - sh);
+  }
+  return neg ? -r : r;
+}
+
+// One entry.  Roundings (u = 2^-53): numerator -> double, / n on the B term; e_i, e_j (one
+// fma each, u8_center_kernel), their product, / n on the e term; then the sum, / 9 (gray) and
+// * alpha on both: at most 7 on either term, the 8 u of the contract (include/deig.h).
+template <int MODE>
+__device__ __forceinline__ double u8_centered_value(long long A, long long Yi, long long Yj,
+                                                    double ei, double ej, int64_t n,
+                                                    double alpha) {
+  const __int128 num = (__int128)n * (__int128)A - (__int128)Yi * (__int128)Yj;
+  const double dn = (double)n;  // exact: n <= 2^40
+  double v = i128_to_double(num) / dn + (ei * ej) / dn;
+  if (MODE == DEIG_U8_GRAY3) v /= 9.0;
+  return v * alpha;
+}
+
+// e_i = fma(-s n, c_i, Y_i + off n): both integers are exact doubles (< 2^53), so e_i is
+// rounded once, relative to itself - it is the small difference s n (mu_i - c_i) when c is a
+// pooled mean next to the own mean mu.  center == NULL: e = 0 (the own mean, exactly).
+// mean_out: mu_i = (Y_i + off n) / (s n), one rounding.  Entries d .. fpad of e are zero.
+template <int MODE>
+__global__ __launch_bounds__(256) void u8_center_kernel(const unsigned long long* __restrict__ colsum,
+                                                        const double* __restrict__ center,
+                                                        int64_t d, int64_t fpad, int64_t n,
+                                                        double* __restrict__ e,
+                                                        double* __restrict__ mean_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= fpad) return;
+  if (i >= d) {
+    e[i] = 0.0;
+    return;
+  }
+  constexpr long long off = MODE == DEIG_U8_GRAY3 ? 384 : 128;
+  constexpr double sc = MODE == DEIG_U8_GRAY3 ? 3.0 : 1.0;
+  const double tot = (double)((long long)colsum[i] + off * n);  // sum of the bytes: exact
+  const double sn = sc * (double)n;
+  e[i] = center ? fma(-sn, center[i], tot) : 0.0;
+  if (mean_out) mean_out[i] = tot / sn;
+}
+
+// Column sums alone (deig_colsum_u8): the bytes (raw) or r + g + b (gray) of 4 features per
+// lane, rows blockIdx.y * 4 + wave, + 4 gridDim.y, ...; uint64 sums, the 4 waves meet in LDS,
+// one integer atomic per feature and block: exact, so the order does not matter.
+template <int MODE>
+__global__ __launch_bounds__(256) void u8_colsum_kernel(const uint8_t* __restrict__ X, int64_t n,
+                                                        int64_t ldx, int64_t d,
+                                                        unsigned long long* __restrict__ acc) {
+  __shared__ unsigned long long cs[4][256];
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int64_t f = (int64_t)blockIdx.x * 256 + lane * 4;
+  unsigned long long sum[4] = {0ull, 0ull, 0ull, 0ull};
+  if (f < d) {  // d % 4 == 0: the 4 features are all in or all out
+    for (int64_t row = (int64_t)blockIdx.y * 4 + g; row < n; row += (int64_t)gridDim.y * 4) {
+      if (MODE == DEIG_U8_RAW) {
+        const uint32_t x = *reinterpret_cast<const uint32_t*>(X + row * ldx + f);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sum[u] += (x >> (8 * u)) & 0xffu;
+      } else {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(X + row * ldx + 3 * f);
+        const uint32_t b[3] = {p[0], p[1], p[2]};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          uint32_t t = 0;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int byte = 3 * u + c;
+            t += (b[byte >> 2] >> (8 * (byte & 3))) & 0xffu;
+          }
+          sum[u] += t;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) cs[g][4 * lane + u] = sum[u];
+  __syncthreads();
+  const int t = threadIdx.x;
+  const int64_t ft = (int64_t)blockIdx.x * 256 + t;
+  if (ft < d) atomicAdd(acc + ft, ((cs[0][t] + cs[1][t]) + cs[2][t]) + cs[3][t]);
+}
+
+// sums[j] as a double: the integer itself (raw: exact, < 2^53) or the integer / 3 (gray:
+// rounded once).
+template <int MODE>
+__global__ __launch_bounds__(256) void u8_colsum_finish_kernel(const unsigned long long* __restrict__ acc,
+                                                               int64_t d, double* __restrict__ sums) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= d) return;
+  const double v = (double)acc[j];
+  sums[j] = MODE == DEIG_U8_GRAY3 ? v / 3.0 : v;
+}
 
 // One item = (plane, lower tile, K segment).  LDS: 2 stages x (A panel, B panel),
 // each panel = 4 row groups x 128 features x 16 B = 8 KiB, the same bytes as the
@@ -185,7 +306,9 @@ struct U8Sched {
 // scales once in double (as u8_finalize_kernel) and stores S[i][j] and S[j][i] -
 // no int64 image, no memset, no atomics, no finalize pass (c1 worker shard: the
 // image path's memset + atomics + finalize were most of its 0.30 ms, r03s).
-template <bool DIRECT>
+// CENTERED (DIRECT only; the image path centres in u8_finalize_kernel): the epilogue's value
+// is u8_centered_value of the same accumulators and column sums; the K loop is the same code.
+template <bool DIRECT, bool CENTERED = false>
 __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[2][2][4 * TB * 16];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -290,6 +413,14 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
         const int64_t i = i0 + 64 * wi + 16 * a + 4 * (lane >> 4) + r;
         civ[a][r] = (long long)s.colsum[i < s.d ? i : s.d - 1];
       }
+    double ejv[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (CENTERED) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
+        ejv[b] = s.e[j < s.d ? j : s.d - 1];
+      }
+    }
     // values of this wave's 64 x 64 block (float for S; S64 stored here, scattered)
     float vf[4][4][4];
 #pragma unroll
@@ -297,12 +428,20 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t i = i0 + 64 * wi + 16 * a + 4 * (lane >> 4) + r;
+        double ei = 0.0;
+        if constexpr (CENTERED) ei = s.e[i < s.d ? i : s.d - 1];
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
-          const long long v64 =
-              (long long)acc[a][b][r] + 128ll * (civ[a][r] + cjv[b]) + 16384ll * s.n;
-          const double v = s.div > 0 ? (double)v64 / (double)s.div : s.alpha * (double)v64;
+          double v;
+          if constexpr (CENTERED) {
+            v = u8_centered_value<DEIG_U8_RAW>((long long)acc[a][b][r], civ[a][r], cjv[b], ei,
+                                               ejv[b], s.n, s.alpha);
+          } else {
+            const long long v64 =
+                (long long)acc[a][b][r] + 128ll * (civ[a][r] + cjv[b]) + 16384ll * s.n;
+            v = s.div > 0 ? (double)v64 / (double)s.div : s.alpha * (double)v64;
+          }
           vf[a][b][r] = (float)v;
           if (s.S64 && active && i < s.d && j < s.d && !(diag && j > i)) {
             s.S64[i * s.lds64 + j] = v;
@@ -392,14 +531,16 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
 // exact quotient (div * 9 is exact); else alpha * a (/ 9).  The fp32 S is that
 // double rounded to float: the correctly rounded value except in the ~2^-29 of
 // cases where the double lands on a float tie (then 1 ulp).
-template <int MODE>
+// CENTERED: u8_centered_value of the same integers (e: the centre terms), no offset terms.
+template <int MODE, bool CENTERED = false>
 __global__ __launch_bounds__(256) void u8_finalize_kernel(const unsigned long long* __restrict__ G,
                                                           const unsigned long long* __restrict__ colsum,
                                                           int64_t fpad, int64_t d, int64_t n,
                                                           double alpha, int64_t div,
                                                           float* __restrict__ S,
                                                           int64_t lds, double* __restrict__ S64,
-                                                          int64_t lds64) {
+                                                          int64_t lds64,
+                                                          const double* __restrict__ e) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= d * d) return;
   const int64_t r = idx / d, c = idx - r * d;
@@ -408,16 +549,23 @@ __global__ __launch_bounds__(256) void u8_finalize_kernel(const unsigned long lo
   long long a;
   double v;
   if (MODE == DEIG_U8_RAW) {
-    a = (long long)G[i * fpad + j] + 128ll * (ci + cj) + 16384ll * n;
-    v = div > 0 ? (double)a / (double)div : alpha * (double)a;
+    a = (long long)G[i * fpad + j];
+    if (!CENTERED) {
+      a += 128ll * (ci + cj) + 16384ll * n;
+      v = div > 0 ? (double)a / (double)div : alpha * (double)a;
+    }
   } else {
     const int64_t pl = fpad * fpad;
     const long long phh = (long long)G[i * fpad + j];
     const long long pll = (long long)G[pl + i * fpad + j];
     const long long pww = (long long)G[2 * pl + i * fpad + j];
-    a = 240ll * phh + 16ll * pww - 15ll * pll + 384ll * (ci + cj) + 147456ll * n;
-    v = div > 0 ? (double)a / (9.0 * (double)div) : alpha * (double)a / 9.0;
+    a = 240ll * phh + 16ll * pww - 15ll * pll;
+    if (!CENTERED) {
+      a += 384ll * (ci + cj) + 147456ll * n;
+      v = div > 0 ? (double)a / (9.0 * (double)div) : alpha * (double)a / 9.0;
+    }
   }
+  if (CENTERED) v = u8_centered_value<MODE>(a, ci, cj, e[i], e[j], n, alpha);
   if (S) S[r * lds + c] = (float)v;
   if (S64) S64[r * lds64 + c] = v;
 }
@@ -448,36 +596,39 @@ U8Layout u8_layout(int64_t n, int64_t d, int mode) {
   return L;
 }
 
-}  // namespace
+// The centred call's workspace: the uncentred layout, then the fpad centre terms e.
+size_t u8_centered_off_e(const U8Layout& L) { return align_up(L.total, 256); }
 
-size_t syrk_u8_workspace_bytes(int64_t n, int64_t d, int mode) {
-  if (n < 1 || d < 1) return 0;
-  return u8_layout(n, d, mode).total;
-}
-
-int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double alpha,
-                   float* S, int64_t lds, double* S64, int64_t lds64, void* ws, size_t ws_bytes,
-                   hipStream_t stream) {
-  DEIG_REQUIRE(mode == DEIG_U8_RAW || mode == DEIG_U8_GRAY3, "syrk_u8: unknown mode %d", mode);
-  DEIG_REQUIRE(n >= 1, "syrk_u8: n must be >= 1 (got %lld)", (long long)n);
+// Both covariances.  centered: S about `center` (nullptr: the own mean), else alpha V^T V.
+int u8_run(const char* what, bool centered, const uint8_t* X, int64_t n, int64_t d, int64_t ldx,
+           int mode, const double* center, double alpha, float* S, int64_t lds, double* S64,
+           int64_t lds64, double* mean_out, void* ws, size_t ws_bytes, hipStream_t stream) {
+  DEIG_REQUIRE(mode == DEIG_U8_RAW || mode == DEIG_U8_GRAY3, "%s: unknown mode %d", what, mode);
+  DEIG_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
   DEIG_REQUIRE(d >= 4 && d % 4 == 0 && d <= (1 << 15),
-               "syrk_u8: d must be a multiple of 4 in [4, 32768] (got %lld)", (long long)d);
+               "%s: d must be a multiple of 4 in [4, 32768] (got %lld)", what, (long long)d);
   const int64_t need = mode == DEIG_U8_RAW ? d : 3 * d;
-  DEIG_REQUIRE(ldx >= need && ldx % 4 == 0, "syrk_u8: ldx must be >= %lld bytes and a multiple of 4",
+  DEIG_REQUIRE(ldx >= need && ldx % 4 == 0, "%s: ldx must be >= %lld bytes and a multiple of 4", what,
                (long long)need);
-  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) & 3u) == 0, "syrk_u8: X must be 4-byte aligned");
-  DEIG_REQUIRE(S || S64, "syrk_u8: need S and/or S64");
-  DEIG_REQUIRE(!S || lds >= d, "syrk_u8: lds must be >= d");
-  DEIG_REQUIRE(!S64 || lds64 >= d, "syrk_u8: lds64 must be >= d");
-  DEIG_REQUIRE(n <= (int64_t(1) << 40), "syrk_u8: n too large");
+  DEIG_REQUIRE(S || S64, "%s: need S and/or S64", what);
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) & 3u) == 0, "%s: X must be 4-byte aligned", what);
+  DEIG_REQUIRE(!S || lds >= d, "%s: lds must be >= d", what);
+  DEIG_REQUIRE(!S64 || lds64 >= d, "%s: lds64 must be >= d", what);
+  DEIG_REQUIRE(n <= (int64_t(1) << 40), "%s: n too large", what);
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % 8 == 0 &&
+                   reinterpret_cast<uintptr_t>(mean_out) % 8 == 0,
+               "%s: center and mean_out must be 8-byte aligned", what);
   const U8Layout L = u8_layout(n, d, mode);
-  if (!ws || ws_bytes < L.total)
-    return fail(DEIG_EWORKSPACE, "syrk_u8: workspace %zu bytes < required %zu", ws_bytes, L.total);
+  const size_t off_e = u8_centered_off_e(L);
+  const size_t total = centered ? off_e + sizeof(double) * (size_t)L.fpad : L.total;
+  if (!ws || ws_bytes < total)
+    return fail(DEIG_EWORKSPACE, "%s: workspace %zu bytes < required %zu", what, ws_bytes, total);
   char* base = static_cast<char*>(ws);
   int* order = reinterpret_cast<int*>(base + L.off_order);
   unsigned long long* col = reinterpret_cast<unsigned long long*>(base + L.off_col);
   unsigned long long* G = reinterpret_cast<unsigned long long*>(base + L.off_G);
   uint8_t* img = reinterpret_cast<uint8_t*>(base + L.off_img);
+  double* e = centered ? reinterpret_cast<double*>(base + off_e) : nullptr;
   const int G_ = num_cus();
   // direct epilogue: raw mode, one K segment (int32 exact), enough tiles to fill half
   // the chip (config 1: 300 tiles of a 3072-feature worker shard)
@@ -494,6 +645,16 @@ int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode
     hipLaunchKernelGGL(u8_prep_kernel<DEIG_U8_GRAY3>, pg, dim3(PREP_THR), 0, stream, X, n, ldx,
                        (int)d, L.fpad, L.nkb, img, col, (int)L.nt, order);
   DEIG_HIP_CHECK(hipGetLastError());
+  if (centered) {  // the centre terms (and the own mean) from the column sums
+    const dim3 cg((unsigned)cdiv(L.fpad, 256));
+    if (mode == DEIG_U8_RAW)
+      hipLaunchKernelGGL(u8_center_kernel<DEIG_U8_RAW>, cg, dim3(256), 0, stream, col, center, d,
+                         L.fpad, n, e, mean_out);
+    else
+      hipLaunchKernelGGL(u8_center_kernel<DEIG_U8_GRAY3>, cg, dim3(256), 0, stream, col, center, d,
+                         L.fpad, n, e, mean_out);
+    DEIG_HIP_CHECK(hipGetLastError());
+  }
   // K segments: enough items to fill the chip twice over, each <= MAX_SEG_KB row
   // blocks (int32 accumulators) and >= 4 (amortise the staging prologue).
   int64_t nseg = direct ? 1 : cdiv(2 * G_, L.T * L.planes);
@@ -519,8 +680,13 @@ int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode
   s.lds = lds;
   s.S64 = S64;
   s.lds64 = lds64;
+  s.e = e;
   if (direct) {
-    hipLaunchKernelGGL(u8_syrk_kernel<true>, dim3((unsigned)L.T, 1u), dim3(SYRK_THR), 0, stream, s);
+    if (centered)
+      hipLaunchKernelGGL((u8_syrk_kernel<true, true>), dim3((unsigned)L.T, 1u), dim3(SYRK_THR), 0,
+                         stream, s);
+    else
+      hipLaunchKernelGGL(u8_syrk_kernel<true>, dim3((unsigned)L.T, 1u), dim3(SYRK_THR), 0, stream, s);
     DEIG_HIP_CHECK(hipGetLastError());
     return DEIG_OK;
   }
@@ -528,14 +694,96 @@ int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode
                      dim3(SYRK_THR), 0, stream, s);
   DEIG_HIP_CHECK(hipGetLastError());
   const dim3 fg((unsigned)cdiv(d * d, 256));
-  if (mode == DEIG_U8_RAW)
-    hipLaunchKernelGGL(u8_finalize_kernel<DEIG_U8_RAW>, fg, dim3(256), 0, stream, G, col, L.fpad, d,
-                       n, alpha, div, S, lds, S64, lds64);
-  else
-    hipLaunchKernelGGL(u8_finalize_kernel<DEIG_U8_GRAY3>, fg, dim3(256), 0, stream, G, col, L.fpad,
-                       d, n, alpha, div, S, lds, S64, lds64);
+  if (mode == DEIG_U8_RAW) {
+    if (centered)
+      hipLaunchKernelGGL((u8_finalize_kernel<DEIG_U8_RAW, true>), fg, dim3(256), 0, stream, G, col,
+                         L.fpad, d, n, alpha, div, S, lds, S64, lds64, e);
+    else
+      hipLaunchKernelGGL(u8_finalize_kernel<DEIG_U8_RAW>, fg, dim3(256), 0, stream, G, col, L.fpad,
+                         d, n, alpha, div, S, lds, S64, lds64, e);
+  } else {
+    if (centered)
+      hipLaunchKernelGGL((u8_finalize_kernel<DEIG_U8_GRAY3, true>), fg, dim3(256), 0, stream, G, col,
+                         L.fpad, d, n, alpha, div, S, lds, S64, lds64, e);
+    else
+      hipLaunchKernelGGL(u8_finalize_kernel<DEIG_U8_GRAY3>, fg, dim3(256), 0, stream, G, col, L.fpad,
+                         d, n, alpha, div, S, lds, S64, lds64, e);
+  }
+  DEIG_HIP_CHECK(hipGetLastError());
+  return DEIG_OK;
+}
+
+}  // namespace
+
+// The shape rules every uint8 entry point shares (d <= dmax); the pointers come after the
+// caller's own shape rules.
+int u8_check_shape(const char* what, int64_t n, int64_t d, int64_t ldx, int mode, int64_t dmax) {
+  DEIG_REQUIRE(mode == DEIG_U8_RAW || mode == DEIG_U8_GRAY3, "%s: unknown mode %d", what, mode);
+  DEIG_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
+  DEIG_REQUIRE(d >= 4 && d % 4 == 0 && d <= dmax, "%s: d must be a multiple of 4 in [4, %lld] (got %lld)",
+               what, (long long)dmax, (long long)d);
+  const int64_t need = mode == DEIG_U8_RAW ? d : 3 * d;
+  DEIG_REQUIRE(ldx >= need && ldx % 4 == 0, "%s: ldx must be >= %lld bytes and a multiple of 4", what,
+               (long long)need);
+  DEIG_REQUIRE(n <= (int64_t(1) << 40), "%s: n too large", what);
+  return DEIG_OK;
+}
+
+size_t syrk_u8_workspace_bytes(int64_t n, int64_t d, int mode) {
+  if (n < 1 || d < 1) return 0;
+  return u8_layout(n, d, mode).total;
+}
+
+int syrk_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double alpha,
+                   float* S, int64_t lds, double* S64, int64_t lds64, void* ws, size_t ws_bytes,
+                   hipStream_t stream) {
+  return u8_run("syrk_u8", false, X, n, d, ldx, mode, nullptr, alpha, S, lds, S64, lds64, nullptr,
+                ws, ws_bytes, stream);
+}
+
+size_t syrk_u8_centered_workspace_bytes(int64_t n, int64_t d, int mode) {
+  if (n < 1 || d < 1) return 0;
+  const U8Layout L = u8_layout(n, d, mode);
+  return u8_centered_off_e(L) + sizeof(double) * (size_t)L.fpad;
+}
+
+int syrk_u8_centered_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                            const double* center, double alpha, float* S, int64_t lds, double* S64,
+                            int64_t lds64, double* mean_out, void* ws, size_t ws_bytes,
+                            hipStream_t stream) {
+  return u8_run("syrk_u8_centered", true, X, n, d, ldx, mode, center, alpha, S, lds, S64, lds64,
+                mean_out, ws, ws_bytes, stream);
+}
+
+size_t colsum_u8_workspace_bytes(int64_t n, int64_t d) {
+  if (n < 1 || d < 1) return 0;
+  return align_up(sizeof(unsigned long long) * (size_t)d, 256);  // the integer sums
+}
+
+int colsum_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double* sums,
+                     void* ws, size_t ws_bytes, hipStream_t stream) {
+  if (int rc = u8_check_shape("colsum_u8", n, d, ldx, mode, int64_t(1) << 31)) return rc;
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) & 3u) == 0, "colsum_u8: X must be 4-byte aligned");
+  DEIG_REQUIRE(sums &&reinterpret_cast<uintptr_t>(sums) % 8 == 0,
+               "colsum_u8: sums must not be NULL (8-byte aligned)");
+  const size_t need = colsum_u8_workspace_bytes(n, d);
+  if (!ws || ws_bytes < need)
+    return fail(DEIG_EWORKSPACE, "colsum_u8: workspace %zu bytes < required %zu", ws_bytes, need);
+  unsigned long long* acc = static_cast<unsigned long long*>(ws);
+  DEIG_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (size_t)d, stream));
+  const int64_t yb = cdiv(n, 4) < 128 ? cdiv(n, 4) : 128;
+  const dim3 grid((unsigned)cdiv(d, 256), (unsigned)yb);
+  const dim3 fg((unsigned)cdiv(d, 256));
+  if (mode == DEIG_U8_RAW) {
+    hipLaunchKernelGGL(u8_colsum_kernel<DEIG_U8_RAW>, grid, dim3(256), 0, stream, X, n, ldx, d, acc);
+    hipLaunchKernelGGL(u8_colsum_finish_kernel<DEIG_U8_RAW>, fg, dim3(256), 0, stream, acc, d, sums);
+  } else {
+    hipLaunchKernelGGL(u8_colsum_kernel<DEIG_U8_GRAY3>, grid, dim3(256), 0, stream, X, n, ldx, d, acc);
+    hipLaunchKernelGGL(u8_colsum_finish_kernel<DEIG_U8_GRAY3>, fg, dim3(256), 0, stream, acc, d, sums);
+  }
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
 }
 
 }  // namespace deig
+

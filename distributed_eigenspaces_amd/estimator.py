@@ -19,7 +19,14 @@ projectors (:126-130).  Here:
 CENTRED covariance: one more collective before the workers run - an all-reduce of the
 float64 column sums and row counts into the pooled mean (``global_mean``) - and every
 logical worker's covariance is taken about that pooled mean
-(``linalg.sigma_hat_centered``), so the shards estimate the same matrix.
+(``linalg.sigma_hat_centered``), so the shards estimate the same matrix.  With
+``u8_mode="raw"`` or ``"gray"`` (opt-in as well) uint8 samples go through that path as bytes:
+the column sums are the integer ones of ``linalg.column_sums_u8`` and every worker's
+covariance is ``linalg.sigma_hat_u8_centered`` about the pooled mean - the exact int8-MFMA
+pipeline with centred epilogues, no widening of the shard.  The features are v = x ("raw":
+one byte each) or v = (r + g + b) / 3 of interleaved pixels ("gray": (n, H, W, 3) or rows of
+3-byte pixels), and ``EstimatorResult.mean`` is in units of v.  Without ``u8_mode`` uint8
+samples are widened to float64 as before.
 
 The collective layer only uses ``torch.distributed`` with tensors on the rank's
 device, so it runs on ``gloo`` with CPU tensors too (multi-process tests); the
@@ -112,16 +119,18 @@ def _batch_accepts(solver_kw: dict) -> bool:
     return all(key in params and key not in ("Ss", "k") for key in solver_kw)
 
 
-def _covariance(x: torch.Tensor, center=None) -> torch.Tensor:
+def _covariance(x: torch.Tensor, center=None, u8_mode=None) -> torch.Tensor:
     """A logical worker's covariance: the reference's uncentred one, or (center=True fits)
-    the covariance about the pooled mean."""
+    the covariance about the pooled mean - of the bytes themselves with ``u8_mode``."""
     if center is None:
         return linalg.sigma_hat(x)
+    if u8_mode is not None:
+        return linalg.sigma_hat_u8_centered(x, center=center, mode=u8_mode)
     return linalg.sigma_hat_centered(x, center=center)
 
 
-def _gpu_worker(x: torch.Tensor, k: int, center=None, **kw):
-    S = _covariance(x, center)
+def _gpu_worker(x: torch.Tensor, k: int, center=None, u8_mode=None, **kw):
+    S = _covariance(x, center, u8_mode)
     r = linalg.topk_eigh(S, k, check_finite=False, **kw)
     return r.V, r.evals, r.sweeps
 
@@ -130,7 +139,7 @@ class DistributedEigenspaceEstimator:
     def __init__(self, k: int, workers_per_rank: int = 1, server_rank: int = 0, group=None,
                  worker_fn=None, solver_kw=None, concurrent_workers: bool = False,
                  batched_workers: bool = True, aggregate: str = "projector",
-                 center: bool = False):
+                 center: bool = False, u8_mode: str | None = None):
         if aggregate not in AGGREGATES:
             raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
         # "projector" (default, the reference's server): top-k of the projector average;
@@ -154,6 +163,18 @@ class DistributedEigenspaceEstimator:
         # center (opt-in): the eigenspace of the covariance about the pooled mean of all
         # ranks' rows; the default stays the reference's uncentred second moment.
         self.center = bool(center)
+        # u8_mode (opt-in, center=True only): uint8 X_local is read as bytes, "raw" or "gray"
+        # (linalg.sigma_hat_u8's modes); None: uint8 is widened to float64 as before.
+        if u8_mode is not None and u8_mode not in ("raw", "gray"):
+            raise ValueError(f"u8_mode must be None, 'raw' or 'gray', got {u8_mode!r}")
+        if u8_mode is not None and not self.center:
+            raise ValueError("u8_mode needs center=True (the uncentred uint8 covariance is "
+                             "linalg.sigma_hat_u8)")
+        self.u8_mode = u8_mode
+
+    def _u8(self, X_local: torch.Tensor):
+        """The uint8 mode this fit runs X_local in (None: the float path)."""
+        return self.u8_mode if X_local.dtype == torch.uint8 else None
 
     def _rank_world(self):
         if dist.is_available() and dist.is_initialized():
@@ -166,7 +187,10 @@ class DistributedEigenspaceEstimator:
         used = self.wpr * (X_local.shape[0] // self.wpr)
         rows = X_local[:used]
         # host tensors: the gloo rehearsal with an injected worker
-        sums = linalg.column_sums(rows) if rows.is_cuda else rows.to(torch.float64).sum(dim=0)
+        if self._u8(X_local) is not None:
+            sums = linalg.column_sums_u8(rows, self.u8_mode)
+        else:
+            sums = linalg.column_sums(rows) if rows.is_cuda else rows.to(torch.float64).sum(dim=0)
         return global_mean(sums, used, self.group)
 
     def local_bases(self, X_local: torch.Tensor, center: torch.Tensor | None = None):
@@ -174,10 +198,13 @@ class DistributedEigenspaceEstimator:
         pooled mean of a centred fit, None = uncentred)."""
         parts = shard_ranges(X_local.shape[0], self.wpr)
         ckw = {} if center is None else {"center": center}
+        u8 = self._u8(X_local) if center is not None else None
+        if u8 is not None:
+            ckw["u8_mode"] = u8
         if self.concurrent and len(parts) > 1 and X_local.is_cuda:
-            return self._local_bases_concurrent(X_local, parts, center)
+            return self._local_bases_concurrent(X_local, parts, center, u8)
         if self.batched and len(parts) > 1 and X_local.is_cuda and _batch_accepts(self.solver_kw):
-            Ss = [_covariance(X_local[lo:hi], center) for lo, hi in parts]
+            Ss = [_covariance(X_local[lo:hi], center, u8) for lo, hi in parts]
             rs = linalg.topk_eigh_batch(Ss, self.k, check_finite=False, **self.solver_kw)
             return (torch.cat([r.V.t() for r in rs], dim=0).contiguous(), [r.evals for r in rs],
                     [r.sweeps for r in rs])
@@ -189,14 +216,14 @@ class DistributedEigenspaceEstimator:
             sw.append(s)
         return torch.cat(rows, dim=0).contiguous(), evs, sw
 
-    def _local_bases_concurrent(self, X_local: torch.Tensor, parts, center=None):
+    def _local_bases_concurrent(self, X_local: torch.Tensor, parts, center=None, u8=None):
         from .my_threading import Slave
         dev = X_local.device
         main = torch.cuda.current_stream(dev)
         slaves = []
         try:
             for lo, hi in parts:
-                S = _covariance(X_local[lo:hi], center)
+                S = _covariance(X_local[lo:hi], center, u8)
                 ev = torch.cuda.Event()
                 ev.record(main)
                 st = torch.cuda.Stream(dev)

@@ -26,6 +26,7 @@ __all__ = [
     "oja_steps", "oja_check", "sym_apply", "sym_power", "sigma_hat_u8", "sigma_hat_shift",
     "procrustes_average", "subspace_distance", "projector_distance", "ProcrustesResult",
     "column_sums", "sigma_hat_centered", "pca_transform",
+    "column_sums_u8", "sigma_hat_u8_centered", "pca_transform_u8",
 ]
 
 DEFAULT_TOL = 1e-6
@@ -312,27 +313,20 @@ def sigma_hat_centered(x: torch.Tensor, center: torch.Tensor | None = None,
     return (S, mean) if return_mean else S
 
 
-def sigma_hat_u8(x: torch.Tensor, mode: str = "auto", alpha: float | None = None,
-                 out: torch.Tensor | None = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    """Exact Sigma_hat of uint8 samples on int8 MFMA (fused ingest, SURVEY.md §8 f2).
-
-    x: uint8 tensor on the GPU (host arrays are copied over), either
-      * (n, d) raw bytes, mode "raw": V = x;
-      * (n, H, W, 3) interleaved pixels (CIFAR layout, load_data.py:18-33), mode
-        "gray": V = x.mean(axis=3).reshape(n, H*W) - the reference's preprocessing
-        distributed.py:170-173 - fused into the covariance; or (n, 3m) rows with
-        mode "gray" explicitly.
-    Returns alpha * V^T V (alpha = 1/n: distributed.py:59-70) as a (d, d) tensor of
-    ``dtype`` (float32: within one ulp of the exact result - a double quotient
-    rounded to float; float64: exact to double rounding).  Every product and sum is an integer computation
-    (include/deig.h deig_syrk_u8), so there is no accumulation error at all.
-    """
+def _u8_samples(x, mode: str, name: str):
+    """The input normalisation of the uint8 ops: ``(x2, mode, n, d, dp)`` with x2 the
+    samples as the library reads them - 2-D uint8 on the device, unit column stride, rows
+    4-byte aligned - ``mode`` resolved ("auto": "gray" for 4-D pixels, else "raw"), d the
+    number of features and dp = d rounded up to a multiple of 4.  Accepts (n, d) raw bytes,
+    (n, H, W, 3) pixels and (n, 3 m) rows of 3-byte pixels with mode "gray".  Whatever does
+    not meet the layout rules is copied into a zero-filled buffer of dp features: the
+    padding features are zero bytes, so they add exact zeros to every sum and product."""
     if not isinstance(x, torch.Tensor):
         x = torch.as_tensor(x)
     if x.dtype != torch.uint8:
-        raise ValueError(f"sigma_hat_u8 needs uint8 samples, got {x.dtype}")
+        raise ValueError(f"{name} needs uint8 samples, got {x.dtype}")
     if not torch.cuda.is_available():
-        raise RuntimeError("sigma_hat_u8: needs a ROCm GPU; there is no CPU fallback")
+        raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
     if x.device.type != "cuda":
         x = x.to(torch.device("cuda", torch.cuda.current_device()))
     if mode == "auto":
@@ -352,16 +346,149 @@ def sigma_hat_u8(x: torch.Tensor, mode: str = "auto", alpha: float | None = None
         if x.dim() != 2:
             raise ValueError(f"raw mode needs a 2-D (n, d) tensor, got {tuple(x.shape)}")
         d = x.shape[1]
-    if n == 0:
-        return torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
-    a = (1.0 / n) if alpha is None else float(alpha)
     width = 3 * d if mode == "gray" else d
     dp = (d + 3) // 4 * 4
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 4 or dp != d:
+    if n > 0 and (x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 4 or dp != d):
         wp = 3 * dp if mode == "gray" else dp
         xx = torch.zeros((n, (wp + 3) // 4 * 4), dtype=torch.uint8, device=x.device)
         xx[:, :width] = x[:, :width]
         x = xx
+    return x, mode, n, d, dp
+
+
+def _pad_vector(v, d: int, dp: int, device, name: str):
+    """(d,) float64 vector on the device, zero-padded to dp entries (None stays None)."""
+    if v is None:
+        return None
+    v = torch.as_tensor(v).to(device=device, dtype=torch.float64).reshape(-1)
+    if v.numel() != d:
+        raise ValueError(f"{name} must hold d = {d} numbers, got {v.numel()}")
+    if dp != d:
+        v = torch.cat([v, torch.zeros(dp - d, dtype=torch.float64, device=device)])
+    return v.contiguous()
+
+
+def column_sums_u8(x: torch.Tensor, mode: str = "auto") -> torch.Tensor:
+    """sums[j] = sum_r v[r, j] of uint8 samples (include/deig.h deig_colsum_u8): a (d,)
+    float64 tensor from an integer accumulation - exact for mode "raw", the integer sum of
+    r + g + b divided by 3 (one rounding) for "gray"; deterministic.  x, mode: as
+    ``sigma_hat_u8``.  The input of the pooled mean of a centred uint8 fit."""
+    x, mode, n, d, dp = _u8_samples(x, mode, "column_sums_u8")
+    sums = torch.zeros(dp, dtype=torch.float64, device=x.device)
+    if n == 0 or d == 0:
+        return sums[:d]
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        nbytes = L.deig_colsum_u8_workspace(n, dp)
+        ws = _workspace(x.device, nbytes)
+        rc = L.deig_colsum_u8(x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode], sums.data_ptr(),
+                              ws.data_ptr(), nbytes, _stream(x.device))
+    _lib.check(rc, "deig_colsum_u8")
+    return sums[:d].contiguous() if dp != d else sums
+
+
+def sigma_hat_u8_centered(x: torch.Tensor, center: torch.Tensor | None = None, mode: str = "auto",
+                          alpha: float | None = None, dtype: torch.dtype = torch.float64,
+                          return_mean: bool = False):
+    """Centred covariance alpha * sum_r (v_r - c)(v_r - c)^T of uint8 samples, alpha = 1/n by
+    default (include/deig.h deig_syrk_u8_centered): the exact integer pipeline of
+    ``sigma_hat_u8`` with centred epilogues - the numerator n sum y_i y_j - Y_i Y_j is formed
+    exactly, the result is float64-grade (8 * 2^-53 relative to the terms, see the header).
+    x, mode: as ``sigma_hat_u8``.  center: (d,) float64 in units of v (the pooled mean of a
+    multi-shard fit), None = this shard's own mean.  Returns a (d, d) tensor of ``dtype``
+    (float64 by default; float32 is its rounding), bit-exactly symmetric; with
+    ``return_mean`` also the shard's own mean ((d,) float64)."""
+    x, mode, n, d, dp = _u8_samples(x, mode, "sigma_hat_u8_centered")
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype must be torch.float32 or torch.float64")
+    if n == 0:
+        S = torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
+        return (S, torch.full((d,), float("nan"), dtype=torch.float64, device=x.device)) \
+            if return_mean else S
+    c = _pad_vector(center, d, dp, x.device, "center")
+    a = (1.0 / n) if alpha is None else float(alpha)
+    S = torch.empty((dp, dp), dtype=dtype, device=x.device)
+    mean = torch.empty(dp, dtype=torch.float64, device=x.device) if return_mean else None
+    f32 = dtype == torch.float32
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        nbytes = L.deig_syrk_u8_centered_workspace(n, dp, _lib.U8_MODES[mode])
+        ws = _workspace(x.device, nbytes)
+        rc = L.deig_syrk_u8_centered(x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode],
+                                     c.data_ptr() if c is not None else None, ctypes.c_double(a),
+                                     S.data_ptr() if f32 else None, dp,
+                                     None if f32 else S.data_ptr(), dp,
+                                     mean.data_ptr() if mean is not None else None, ws.data_ptr(),
+                                     nbytes, _stream(x.device))
+    _lib.check(rc, "deig_syrk_u8_centered")
+    if dp != d:
+        S = S[:d, :d].contiguous()
+        mean = mean[:d].contiguous() if mean is not None else None
+    return (S, mean) if return_mean else S
+
+
+def pca_transform_u8(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = None,
+                     mode: str = "auto", *, residual: bool = False, energy: bool = False):
+    """``pca_transform`` of uint8 samples, the bytes read once (include/deig.h
+    deig_pca_transform_u8): Y = (V - mean) W with V the features of X (X, mode: as
+    ``sigma_hat_u8``), mean (d,) in units of v or None (no centring), W (d, k) any layout
+    with k <= 256.  Centred in double when the bytes are staged, before the product.
+    Returns Y, or the tuple (Y[, residual][, energy]) as ``pca_transform``."""
+    X, mode, n, d, dp = _u8_samples(X, mode, "pca_transform_u8")
+    W = require_device_tensor(W, "W")
+    if W.dim() != 2:
+        raise ValueError(f"W must be 2-D (d, k), got shape {tuple(W.shape)}")
+    k = W.shape[1]
+    if not 1 <= k <= 256:
+        raise ValueError(f"k={k} out of range [1, 256]")
+    if W.shape[0] != d:
+        raise ValueError(f"shape mismatch: X has {d} features, W has {W.shape[0]} rows")
+    dev = X.device
+    mu = _pad_vector(mean, d, dp, dev, "mean")
+    if dp != d:  # zero bytes, zero rows of W, zero mean entries
+        Wp = torch.zeros((dp, k), dtype=torch.float32, device=W.device)
+        Wp[:d] = W
+        W = Wp
+    W = W.to(dev).t().contiguous().t()  # column-major
+    Y = torch.empty((n, k), dtype=torch.float32, device=dev)
+    res = torch.empty(n, dtype=torch.float32, device=dev) if residual else None
+    en = torch.empty(n, dtype=torch.float32, device=dev) if energy else None
+    if n > 0:
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            nbytes = L.deig_pca_transform_u8_workspace(n, dp, k)
+            ws = _workspace(dev, nbytes)
+            rc = L.deig_pca_transform_u8(X.data_ptr(), n, dp, X.stride(0), _lib.U8_MODES[mode],
+                                         mu.data_ptr() if mu is not None else None, W.data_ptr(),
+                                         k, _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k),
+                                         res.data_ptr() if residual else None,
+                                         en.data_ptr() if energy else None, ws.data_ptr(), nbytes,
+                                         _stream(dev))
+        _lib.check(rc, "deig_pca_transform_u8")
+    if not residual and not energy:
+        return Y
+    return tuple(t for t in (Y, res, en) if t is not None)
+
+
+def sigma_hat_u8(x: torch.Tensor, mode: str = "auto", alpha: float | None = None,
+                 out: torch.Tensor | None = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Exact Sigma_hat of uint8 samples on int8 MFMA (fused ingest, SURVEY.md §8 f2).
+
+    x: uint8 tensor on the GPU (host arrays are copied over), either
+      * (n, d) raw bytes, mode "raw": V = x;
+      * (n, H, W, 3) interleaved pixels (CIFAR layout, load_data.py:18-33), mode
+        "gray": V = x.mean(axis=3).reshape(n, H*W) - the reference's preprocessing
+        distributed.py:170-173 - fused into the covariance; or (n, 3m) rows with
+        mode "gray" explicitly.
+    Returns alpha * V^T V (alpha = 1/n: distributed.py:59-70) as a (d, d) tensor of
+    ``dtype`` (float32: within one ulp of the exact result - a double quotient
+    rounded to float; float64: exact to double rounding).  Every product and sum is an integer computation
+    (include/deig.h deig_syrk_u8), so there is no accumulation error at all.
+    """
+    x, mode, n, d, dp = _u8_samples(x, mode, "sigma_hat_u8")
+    if n == 0:
+        return torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
+    a = (1.0 / n) if alpha is None else float(alpha)
     if dtype not in (torch.float32, torch.float64):
         raise ValueError("dtype must be torch.float32 or torch.float64")
     direct = (out is not None and dp == d and out.dtype == dtype and out.device == x.device

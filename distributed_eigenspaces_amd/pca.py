@@ -14,8 +14,15 @@ is the opt-in centred counterpart:
   descending variance, and gives ``explained_variance_``.
 * ``transform`` / ``reconstruction_error``: the fused centred transform kernel.
 
-Float32 and float64 samples; uint8 samples are rejected (centring on top of the exact
-integer covariance is a follow-up).
+Float32 and float64 samples by default.  uint8 samples are opt-in through
+``PCA(k, u8_mode="raw")`` (features v = x, one byte each) or ``u8_mode="gray"``
+(v = (r + g + b) / 3 of (n, H, W, 3) pixels or rows of 3-byte pixels): the bytes then go
+through the whole stack as bytes - integer column sums into the pooled mean, the exact
+int8-MFMA covariance with centred epilogues (``linalg.sigma_hat_u8_centered``) in every
+worker, and ``linalg.pca_transform_u8`` (the bytes staged and centred in the kernel) for the
+second pass of ``fit``, ``transform`` and ``reconstruction_error``.  ``mean_`` and
+``components_`` are in units of v; ``inverse_transform`` returns float v-space rows.
+Without ``u8_mode`` uint8 samples are rejected with a ``TypeError``.
 """
 from __future__ import annotations
 
@@ -44,7 +51,10 @@ class PCA:
     """
 
     def __init__(self, k: int, *, workers_per_rank: int = 1, group=None,
-                 aggregate: str = "projector", solver_kw=None):
+                 aggregate: str = "projector", solver_kw=None, u8_mode: str | None = None):
+        if u8_mode is not None and u8_mode not in ("raw", "gray"):
+            raise ValueError(f"u8_mode must be None, 'raw' or 'gray', got {u8_mode!r}")
+        self.u8_mode = u8_mode
         self.k = int(k)
         self.wpr = int(workers_per_rank)
         self.group = group
@@ -57,14 +67,22 @@ class PCA:
         self.explained_variance_ratio_ = None
         self.n_samples_ = 0
 
-    @staticmethod
-    def _samples(X, what: str) -> torch.Tensor:
+    def _samples(self, X, what: str) -> torch.Tensor:
         if not isinstance(X, torch.Tensor):
             X = torch.as_tensor(X)
         if X.dtype == torch.uint8:
-            raise TypeError(f"PCA.{what}: uint8 samples are not supported yet - centring on top of "
-                            "the exact int8 covariance (linalg.sigma_hat_u8) is a follow-up; "
-                            "convert to float32 or float64")
+            if self.u8_mode is None:
+                raise TypeError(f"PCA.{what}: uint8 samples need the keyword u8_mode='raw' (one "
+                                "byte per feature) or u8_mode='gray' (3-byte pixels) in PCA(...); "
+                                "or convert to float32 or float64")
+            if X.dim() != 2 and not (self.u8_mode == "gray" and X.dim() == 4):
+                raise ValueError(f"PCA.{what}: uint8 samples must be 2-D, or (n, H, W, 3) pixels "
+                                 f"with u8_mode='gray', got {tuple(X.shape)}")
+            if not torch.cuda.is_available():
+                raise RuntimeError(f"PCA.{what}: needs a ROCm GPU; there is no CPU fallback")
+            if X.device.type != "cuda":
+                X = X.to(torch.device("cuda", torch.cuda.current_device()))
+            return X
         if X.dtype not in (torch.float32, torch.float64):
             raise TypeError(f"PCA.{what}: samples must be float32 or float64, got {X.dtype}")
         if X.dim() != 2:
@@ -84,15 +102,15 @@ class PCA:
         est = DistributedEigenspaceEstimator(k, workers_per_rank=self.wpr, group=self.group,
                                              server_rank=self.server_rank,
                                              aggregate=self.aggregate, solver_kw=self.solver_kw,
-                                             center=True)
+                                             center=True, u8_mode=self.u8_mode)
         r = est.fit(X)
-        d = X.shape[1]
+        d = r.mean.numel()  # the features (of a gray fit: the pixels)
         Vt = torch.empty((k, d), dtype=torch.float32, device=X.device)
         if r.V is not None:
             Vt.copy_(r.V.t())
         broadcast_basis(Vt, self.server_rank, self.group)
         used = self.wpr * (X.shape[0] // self.wpr)
-        Y, en = linalg.pca_transform(X[:used], Vt.t(), r.mean, energy=True)
+        Y, en = self._transform(X[:used], Vt.t(), r.mean, energy=True)
         Y64 = Y.to(torch.float64)
         stats = torch.cat([(Y64.t() @ Y64).reshape(-1), en.to(torch.float64).sum().reshape(1),
                            torch.tensor([float(used)], dtype=torch.float64, device=X.device)])
@@ -110,6 +128,12 @@ class PCA:
         self.n_samples_ = N
         return self
 
+    def _transform(self, X, W, mean, **kw):
+        """The fused transform of the samples' kind: bytes stay bytes (u8_mode)."""
+        if X.dtype == torch.uint8:
+            return linalg.pca_transform_u8(X, W, mean, self.u8_mode, **kw)
+        return linalg.pca_transform(X, W, mean, **kw)
+
     def _fitted(self):
         if self.components_ is None:
             raise RuntimeError("PCA: call fit first")
@@ -117,14 +141,14 @@ class PCA:
     def transform(self, X) -> torch.Tensor:
         """Scores (X - mean_) components_^T, (n, k) float32, one fused pass over X."""
         self._fitted()
-        return linalg.pca_transform(self._samples(X, "transform"), self.components_.t(), self.mean_)
+        return self._transform(self._samples(X, "transform"), self.components_.t(), self.mean_)
 
     def reconstruction_error(self, X) -> torch.Tensor:
         """||(x_i - mean_) - P (x_i - mean_)||^2 per row, P the projector onto the
         components (the kernel's residual: accurate to a multiple of eps ||x_i - mean_||^2)."""
         self._fitted()
-        return linalg.pca_transform(self._samples(X, "reconstruction_error"),
-                                    self.components_.t(), self.mean_, residual=True)[1]
+        return self._transform(self._samples(X, "reconstruction_error"),
+                               self.components_.t(), self.mean_, residual=True)[1]
 
     def inverse_transform(self, Y) -> torch.Tensor:
         """mean_ + Y components_, (n, d) float32 (plain torch.addmm: not a hot path)."""

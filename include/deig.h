@@ -46,7 +46,10 @@ extern "C" {
 
 /* Library version, e.g. 0x000400 for 0.4.0.  A caller built against an older header
  * should compare it with the version it was built for before binding entry points
- * whose signature changed (deig_topk_sym_batch: see below). */
+ * whose signature changed (deig_topk_sym_batch: see below).  The uint8 centred-PCA entry
+ * points (deig_colsum_u8, deig_syrk_u8_centered, deig_pca_transform_u8 and their workspace
+ * queries) are additive: they came without a version change (0x000600), so probe for the
+ * symbols rather than for a version. */
 int deig_version(void);
 
 /* Release the library's process-lifetime host resources (the pinned per-cycle status
@@ -158,6 +161,45 @@ int deig_syrk_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, 
                  float* S, int64_t lds, double* S64, int64_t lds64, void* ws, size_t ws_bytes,
                  void* stream);
 size_t deig_syrk_u8_workspace(int64_t n, int64_t d, int mode);
+
+/* Column sums of the uint8 features in double: sums[j] = sum_r v_rj, v as for deig_syrk_u8
+ * (mode, rows, ldx and alignment rules as there; any d % 4 == 0).  The accumulation is in
+ * integers (one exact integer add per row, in any order: deterministic): DEIG_U8_RAW gives
+ * the exact integer sum, DEIG_U8_GRAY3 the integer sum of r + g + b divided by 3, rounded
+ * once.  sums: d doubles on the device.  The input of the pooled-mean all-reduce of a centred
+ * fit, as deig_colsum is for floats.  Asynchronous on `stream`, no allocation, no
+ * synchronisation; argument errors are DEIG_EINVAL and a short workspace DEIG_EWORKSPACE
+ * before any GPU work. */
+int deig_colsum_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode, double* sums,
+                   void* ws, size_t ws_bytes, void* stream);
+size_t deig_colsum_u8_workspace(int64_t n, int64_t d);
+
+/* Centred covariance of uint8 samples (opt-in, as deig_syrk_centered is for floats):
+ *   S = alpha * sum_r (v_r - c)(v_r - c)^T,   v as for deig_syrk_u8 (same X, n, d, ldx, mode
+ * rules, n <= 2^40), c = center: d doubles on the device in units of v, NULL = the shard's own
+ * mean.  mean_out (optional, d doubles on the device) receives the own mean.  S (fp32) and/or
+ * S64 may be requested, not neither; both triangles are written from the same lower-triangle
+ * value (bit-exact symmetry) and S is S64's double rounded to float.
+ * The deig_syrk_u8 pipeline with centred epilogues: from the integers it already holds -
+ * A_ij = sum y_i y_j and Y_i = sum y_i of the offset values y (raw: x - 128; gray:
+ * r + g + b - 384) -
+ *   s^2 sum (v - c)(v - c)^T = (n A_ij - Y_i Y_j) / n + e_i e_j / n,     s = 1 (raw), 3 (gray),
+ *   e_i = fma(-s n, c_i, Y_i + off n),  off = 128 (raw), 384 (gray);  e = 0 for center == NULL.
+ * The numerator n A_ij - Y_i Y_j is formed exactly in 128-bit integers (either term passes
+ * 2^63 from n ~ 2^25 while the difference stays small) and e_i is rounded once, relative to
+ * itself (both of the fma's integer operands are exact doubles).
+ * Accuracy contract, with u = 2^-53 and B_ij = (n A_ij - Y_i Y_j) / n exactly:
+ *   |S64_ij - exact_ij| <= 8 u (alpha / s^2) (|B_ij| + |e_i e_j| / n),
+ * "exact" being the rational value for the `center` and `alpha` doubles as given.  The 8
+ * counts roundings: the B term sees numerator -> double, / n, the sum, / s^2, * alpha (5); the
+ * e term sees e_i, e_j, their product, / n, the sum, / s^2, * alpha (7); (1 + u)^7 - 1 < 8 u.
+ * Workspace: deig_syrk_u8_centered_workspace(n, d, mode) (>= deig_syrk_u8_workspace: the d
+ * centre terms more).  Asynchronous on `stream`, no allocation, no synchronisation; argument
+ * errors are DEIG_EINVAL and a short workspace DEIG_EWORKSPACE before any GPU work. */
+int deig_syrk_u8_centered(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                          const double* center, double alpha, float* S, int64_t lds, double* S64,
+                          int64_t lds64, double* mean_out, void* ws, size_t ws_bytes, void* stream);
+size_t deig_syrk_u8_centered_workspace(int64_t n, int64_t d, int mode);
 
 /* Subspace size the solvers use for a given k when the caller passes p <= 0. */
 int deig_default_subspace(int64_t d, int k);
@@ -465,6 +507,22 @@ int deig_pca_transform_f32(const float* X, int64_t n, int64_t d, int64_t ldx, co
                            const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
                            float* energy, void* ws, size_t ws_bytes, void* stream);
 size_t deig_pca_transform_workspace(int64_t n, int64_t d, int k);
+
+/* The same transform from uint8 samples, the bytes read once:
+ *   Y = (V - 1 mean^T) W,  energy, resid  as deig_pca_transform_f32 (1 <= k <= 256, any
+ * ldy >= k, each output optional but not all three NULL, mean == NULL: no centring), V the
+ * features of X as for deig_syrk_u8 (mode, ldx in bytes, d % 4 == 0, X 4-byte aligned);
+ * `mean` is in units of v.  Centred when the bytes are staged: t = fl32((double)v - mean),
+ * formed in double and rounded once before the product; DEIG_U8_GRAY3 uses
+ * v = (r + g + b) / 3.0 in double.  Rows past n and features past d contribute exact zeros;
+ * no byte behind column d (3 d for gray) of a row is read.  The accuracy notes, the
+ * parallelisation (one workgroup per 64 rows), the determinism and the workspace (the packed
+ * W image) are those of deig_pca_transform_f32. */
+int deig_pca_transform_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
+                          const double* mean, const float* W, int k, int64_t ldw, float* Y,
+                          int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
+                          void* stream);
+size_t deig_pca_transform_u8_workspace(int64_t n, int64_t d, int k);
 
 /* Building block of the solvers, exposed for direct testing / reuse:
  * C[M x N] = alpha * op(A) * B + beta * C  on fp32 MFMA (16x16x4), N % 16 == 0, N <= 256.
