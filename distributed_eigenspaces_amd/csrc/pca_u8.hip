@@ -5,10 +5,10 @@
 // resid, energy as deig_pca_transform_f32 (pca.hip).  The bytes are read once: a quarter
 // (raw) or three quarters (gray) of what the float kernel reads for the same features.
 //
-// A sibling of pca_transform_kernel (pca.hip, left as it is: its measured times are on
-// record): the same 64-row block tile, 4 waves x (16 rows x kp) on v_mfma_f32_16x16x4_f32,
-// 32-slot chunks of fp32 values double-buffered in LDS, the same epilogue, no atomics.  What
-// differs is how a chunk is staged:
+// The block tile, the W chunk's LDS store and the MFMA chunk product are skinny_tile.hpp's,
+// shared with pca_transform_kernel (pca.hip); the epilogue is that header's too, as text
+// (see the end of the kernel); no atomics.  This kernel's
+// own is how a chunk is staged (and with it which rows of W a chunk loads):
 //  * the float kernel gives 8 threads to a row and 16 B (4 floats) to a thread per 32-column
 //    chunk.  With bytes that map would load 4 B per thread and 32-B row segments.  Here the
 //    unit of loading is a SUPER-CHUNK of 128 features: 8 threads per row, 16 features per
@@ -41,7 +41,7 @@
 // fewer than 13 features left runs only the compute chunks that hold any (d % 128 in 4 ..
 // 12: 1 .. 3 chunks), so d = 4 costs one chunk; d = 36 costs four partly filled ones where
 // the float kernel has two - small d is not this kernel's case.
-#include "deig_internal.hpp"
+#include "skinny_tile.hpp"
 
 namespace deig {
 namespace {
@@ -49,11 +49,10 @@ namespace {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));  // rows are only 4-byte aligned
 
-constexpr int QBM = 64;         // rows of a block tile
-constexpr int QBK = 32;         // LDS slots (features) per compute chunk
-constexpr int QSK = 128;        // features per super-chunk (4 compute chunks)
-constexpr int QT = 256;         // threads
-constexpr int QAST = QBM;       // row stride of a staged slot: no padding, XOR-swizzled rows
+constexpr int QBM = tile::kRows, QT = tile::kThreads;
+constexpr int QBK = tile::kChunk;  // LDS slots (features) per compute chunk
+constexpr int QSK = 4 * QBK;       // features per super-chunk (4 compute chunks)
+constexpr int QAST = QBM;          // row stride of a staged slot: no padding, XOR-swizzled rows
 
 // Staged values: slot sl (feature of the chunk) x row, at sl * QAST + (row ^ a_swz(sl)).
 // Both sides of the LDS are then free of bank conflicts (32 banks of 4 B per 32-lane half):
@@ -66,11 +65,6 @@ constexpr int QAST = QBM;       // row stride of a staged slot: no padding, XOR-
 //    the other 16 banks.
 __device__ __forceinline__ int a_swz(int sl) { return (sl & 28) ^ ((sl & 1) << 4); }
 
-__host__ __device__ constexpr int pca_u8_bstride(int N) { return (N % 32 == 0) ? N + 16 : N; }
-constexpr size_t pca_u8_shm_bytes(int N) {
-  return (size_t)(2 * QBK * QAST + 2 * QBK * pca_u8_bstride(N)) * sizeof(float);
-}
-
 template <int NB, int MODE>
 __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
     const uint8_t* __restrict__ X, int64_t ldx, const double* __restrict__ mean,
@@ -78,15 +72,13 @@ __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
     float* __restrict__ energy, int64_t n, int64_t d, int k) {
   constexpr int N = NB * 16;
   constexpr int KA = NB == 1 ? 2 : 1;  // accumulators per fragment
-  constexpr int BST = pca_u8_bstride(N);
-  constexpr int NB4 = QBK * N / 4;          // float4s of a W chunk
-  constexpr int BPT = (NB4 + QT - 1) / QT;  // per thread
+  constexpr int BST = tile::bstride(N);
+  constexpr int NB4 = QBK * N / 4, BPT = tile::b_per_thread(NB);  // float4s per chunk, per thread
   constexpr int BPF = MODE == DEIG_U8_GRAY3 ? 3 : 1;  // bytes per feature
   constexpr int DW = 4 * BPF;  // dwords a thread holds per row and super-chunk
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                   // [2][QBK][QAST]
   float* Bs = smem + 2 * QBK * QAST;  // [2][QBK][BST]
-  float* es = smem;                   // [QBM] row energies, on the dead staging buffers (pca.hip)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -164,7 +156,6 @@ __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
   // to zero, features past d are zero bytes against a zero mean
   auto store = [&](int buf, const uint32_t (&x)[2][DW], int c) {
     float* as = As + buf * QBK * QAST;
-    float* bs = Bs + buf * QBK * BST;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
 #pragma unroll
@@ -194,14 +185,7 @@ __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
         as[(4 * kq + e) * QAST + ((mm + 32 * u) ^ a_swz(4 * kq + e))] = t;
       }
     }
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      const int f = tid + QT * u;
-      if (f < NB4) {
-        const int slot = f / (N / 4), c4 = f % (N / 4);
-        *reinterpret_cast<f32x4*>(bs + slot * BST + 4 * c4) = rb[u];
-      }
-    }
+    tile::store_b<NB>(Bs + buf * QBK * BST, rb, tid);
   };
 
   const int r = lane & 15, kk = lane >> 4;
@@ -231,15 +215,9 @@ __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
         }
         const int cur = c & 1;
         const float* as = As + cur * QBK * QAST + kk * QAST;
-        const float* bs = Bs + cur * QBK * BST + kk * BST + r;
-#pragma unroll
-        for (int s = 0; s < QBK / 4; ++s) {
-          const float a = as[4 * s * QAST + (arow ^ (4 * s))];  // a_swz(4 s + kk), kk's bit in arow
-#pragma unroll
-          for (int j = 0; j < NB; ++j)
-            acc[j][s % KA] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bs[4 * s * BST + 16 * j],
-                                                                  acc[j][s % KA], 0, 0, 0);
-        }
+        // a_swz(4 s + kk), kk's bit in arow
+        tile::mfma_chunk(acc, Bs + cur * QBK * BST, r, kk,
+                         [&](int s) { return as[4 * s * QAST + (arow ^ (4 * s))]; });
         if (more) {
           if (within)
             store(cur ^ 1, xa, (c + 1) & 3);
@@ -257,7 +235,9 @@ __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
     }
   }
 
-  // row energies: the 8 staging threads of a row are 8 consecutive lanes
+  // The text of tile::transform_epilogue.  Called as the helper, this kernel's K loop issues
+  // one of the staging's packed energy fmas (v_pk_fma_f32) as two scalar ones.
+  float* es = smem;
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     float e = en[u];
@@ -268,7 +248,6 @@ __global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
   }
   __syncthreads();
 
-  // C/D map of 16x16x4: col = lane & 15, row = 4 * (lane >> 4) + reg
   const int lrow = 16 * wave + 4 * kk;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -300,36 +279,17 @@ __global__ __launch_bounds__(256) void pad_mean_kernel(const double* __restrict_
   if (i < dpad) out[i] = i < d ? mean[i] : 0.0;
 }
 
-template <int NB, int MODE>
-int pca_u8_launch_nb(const uint8_t* X, int64_t ldx, const double* mean, const float* Wr, float* Y,
-                     int64_t ldy, float* resid, float* energy, int64_t n, int64_t d, int k,
-                     hipStream_t st) {
-  constexpr size_t shm = pca_u8_shm_bytes(NB * 16);
-  // once per instantiation (C++11 thread-safe static initialisation)
-  static const hipError_t attr =
-      hipFuncSetAttribute((const void*)pca_transform_u8_kernel<NB, MODE>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  DEIG_HIP_CHECK(attr);
-  hipLaunchKernelGGL((pca_transform_u8_kernel<NB, MODE>), dim3((unsigned)cdiv(n, QBM)), dim3(QT),
-                     shm, st, X, ldx, mean, Wr, Y, ldy, resid, energy, n, d, k);
-  DEIG_HIP_CHECK(hipGetLastError());
-  return DEIG_OK;
-}
-
 template <int MODE>
 int pca_u8_dispatch(int kp, const uint8_t* X, int64_t ldx, const double* mean, const float* Wr,
                     float* Y, int64_t ldy, float* resid, float* energy, int64_t n, int64_t d, int k,
                     hipStream_t st) {
-  switch (kp / 16) {
-#define DEIG_NB(x) \
-  case x:          \
-    return pca_u8_launch_nb<x, MODE>(X, ldx, mean, Wr, Y, ldy, resid, energy, n, d, k, st);
-    DEIG_NB(1) DEIG_NB(2) DEIG_NB(3) DEIG_NB(4) DEIG_NB(5) DEIG_NB(6) DEIG_NB(7) DEIG_NB(8)
-    DEIG_NB(9) DEIG_NB(10) DEIG_NB(11) DEIG_NB(12) DEIG_NB(13) DEIG_NB(14) DEIG_NB(15)
-    DEIG_NB(16)
-#undef DEIG_NB
-  }
-  return fail(DEIG_EINVAL, "pca_transform_u8: unsupported k = %d", k);
+  const dim3 grid((unsigned)cdiv(n, QBM));
+  const int rc = tile::dispatch_nb(kp / 16, [&](auto nb) {
+    return tile::launch<pca_transform_u8_kernel<nb(), MODE>>(
+        grid, tile::shm_bytes(nb() * 16, QAST), st, X, ldx, mean, Wr, Y, ldy, resid, energy, n, d, k);
+  });
+  if (rc == tile::kNoSuchNb) return fail(DEIG_EINVAL, "pca_transform_u8: unsupported k = %d", k);
+  return rc;
 }
 
 }  // namespace

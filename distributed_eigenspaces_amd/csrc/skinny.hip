@@ -11,28 +11,20 @@
 // streams S once: at p <= ~40 it is HBM-bound (4 d^2 bytes), above that it is
 // MFMA-bound (2 d^2 p flops).
 //
-// Block = 4 waves; block tile 64 (M) x N, each wave 16 rows x N (N/16 MFMA
-// accumulators).  K advances in chunks of 32 staged through LDS (register
-// staging, double buffered, written after the compute of the previous chunk).
-// LDS images are k-major ([k][m] and [k][n]) with row strides == 16 (mod 32)
-// so the two 16-lane halves of a ds_read_b32 group hit disjoint banks.
-// Split-K over gridDim.y writes fp32 partial slabs; skinny_reduce_kernel sums
-// them in slice order (deterministic).
+// The block tile, its LDS images, the B chunk store and the MFMA chunk product are
+// skinny_tile.hpp's, with the padded A layout and one accumulator per fragment.  This
+// kernel's own: both forms of A (TRANS), batched problems (blockIdx.z), and split-K over
+// gridDim.y, which writes fp32 partial slabs that skinny_reduce_kernel sums in slice order
+// (deterministic).
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "deig_internal.hpp"
+#include "skinny_tile.hpp"
 
 namespace deig {
 namespace {
 
-constexpr int SBM = 64;
-constexpr int SBK = 32;
-constexpr int ST = 256;
-constexpr int AST = SBM + 16;  // 80 == 16 mod 32
-
-__host__ __device__ constexpr int bstride(int N) { return (N % 32 == 0) ? N + 16 : N; }
+constexpr int SBM = tile::kRows, SBK = tile::kChunk;
+constexpr int ST = tile::kThreads, AST = tile::kAStridePadded;
 
 template <int NB, bool TRANS>
 __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A, int64_t lda,
@@ -48,9 +40,8 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
     C = reinterpret_cast<float*>(reinterpret_cast<char*>(C) + o);
     part = reinterpret_cast<float*>(reinterpret_cast<char*>(part) + o);
   }
-  constexpr int BST = bstride(N);
-  constexpr int NB4 = SBK * N / 4;                 // float4s of a B chunk
-  constexpr int BPT = (NB4 + ST - 1) / ST;         // per thread
+  constexpr int BST = tile::bstride(N);
+  constexpr int NB4 = SBK * N / 4, BPT = tile::b_per_thread(NB);  // float4s per chunk, per thread
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                      // [2][SBK][AST]
   float* Bs = smem + 2 * SBK * AST;      // [2][SBK][BST]
@@ -62,9 +53,9 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
   const int ks = gridDim.y, sl = blockIdx.y;
   const int64_t c0 = nch * sl / ks, c1 = nch * (sl + 1) / ks;
 
-  f32x4 acc[NB];
+  f32x4 acc[NB][1];
 #pragma unroll
-  for (int j = 0; j < NB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < NB; ++j) acc[j][0] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   f32x4 ra[2];
   f32x4 rb[BPT];
@@ -100,7 +91,6 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
   };
   auto store = [&](int buf) {
     float* as = As + buf * SBK * AST;
-    float* bs = Bs + buf * SBK * BST;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int f = tid + ST * u;
@@ -113,14 +103,7 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
         for (int e = 0; e < 4; ++e) as[(4 * kq + e) * AST + mm] = ra[u][e];
       }
     }
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      const int f = tid + ST * u;
-      if (f < NB4) {
-        const int row = f / (N / 4), c4 = f % (N / 4);
-        *reinterpret_cast<f32x4*>(bs + row * BST + 4 * c4) = rb[u];
-      }
-    }
+    tile::store_b<NB>(Bs + buf * SBK * BST, rb, tid);
   };
 
   const int r = lane & 15, kk = lane >> 4;
@@ -133,22 +116,13 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
       const bool more = ch + 1 < c1;
       if (more) load(ch + 1);
       const float* as = As + cur * SBK * AST + kk * AST + 16 * wave + r;
-      const float* bs = Bs + cur * SBK * BST + kk * BST + r;
-#pragma unroll
-      for (int s = 0; s < SBK / 4; ++s) {
-        const float a = as[4 * s * AST];
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bs[4 * s * BST + 16 * j], acc[j], 0, 0,
-                                                       0);
-      }
+      tile::mfma_chunk(acc, Bs + cur * SBK * BST, r, kk, [&](int s) { return as[4 * s * AST]; });
       if (more) store(cur ^ 1);
       __syncthreads();
       cur ^= 1;
     }
   }
 
-  // C/D map of 16x16x4: col = lane & 15, row = 4 * (lane >> 4) + reg
   const int64_t mrow = m0 + 16 * wave + 4 * kk;
   if (ks == 1) {
 #pragma unroll
@@ -158,7 +132,7 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
         const int64_t m = mrow + e;
         if (m < M) {
           float* cp = C + m * ldc + 16 * j + r;
-          const float v = alpha * acc[j][e];
+          const float v = alpha * acc[j][0][e];
           *cp = (beta != 0.0f) ? v + beta * *cp : v;
         }
       }
@@ -169,7 +143,7 @@ __global__ __launch_bounds__(ST) void skinny_kernel(const float* __restrict__ A,
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int64_t m = mrow + e;
-        if (m < M) pp[m * N + 16 * j + r] = acc[j][e];
+        if (m < M) pp[m * N + 16 * j + r] = acc[j][0][e];
       }
   }
 }
@@ -198,38 +172,17 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* __restr
   *cp = (beta != 0.0f) ? v + beta * *cp : v;
 }
 
-template <int NB, bool TRANS>
-int launch_nb(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
-              int64_t M, int64_t K, float alpha, float beta, float* part, int ks,
-              hipStream_t st, const ProbBatch& pbt) {
-  constexpr int N = NB * 16;
-  const size_t shm = (size_t)(2 * SBK * AST + 2 * SBK * bstride(N)) * sizeof(float);
-  // once per instantiation (C++11 thread-safe static initialisation)
-  static const hipError_t attr = hipFuncSetAttribute(
-      (const void*)skinny_kernel<NB, TRANS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  DEIG_HIP_CHECK(attr);
-  dim3 grid((unsigned)cdiv(M, SBM), (unsigned)ks, (unsigned)pbt.n);
-  hipLaunchKernelGGL((skinny_kernel<NB, TRANS>), grid, dim3(ST), shm, st, A, lda, B, ldb, C, ldc,
-                     M, K, alpha, beta, part, pbt);
-  DEIG_HIP_CHECK(hipGetLastError());
-  return DEIG_OK;
-}
-
 template <bool TRANS>
 int launch_t(int NB, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
              int64_t ldc, int64_t M, int64_t K, float alpha, float beta, float* part, int ks,
              hipStream_t st, const ProbBatch& pbt) {
-  switch (NB) {
-#define DEIG_NB(x) \
-  case x:          \
-    return launch_nb<x, TRANS>(A, lda, B, ldb, C, ldc, M, K, alpha, beta, part, ks, st, pbt);
-    DEIG_NB(1) DEIG_NB(2) DEIG_NB(3) DEIG_NB(4) DEIG_NB(5) DEIG_NB(6) DEIG_NB(7) DEIG_NB(8)
-    DEIG_NB(9) DEIG_NB(10) DEIG_NB(11) DEIG_NB(12) DEIG_NB(13) DEIG_NB(14) DEIG_NB(15)
-    DEIG_NB(16)
-#undef DEIG_NB
-    default:
-      return fail(DEIG_EINVAL, "skinny: unsupported N = %d", NB * 16);
-  }
+  const dim3 grid((unsigned)cdiv(M, SBM), (unsigned)ks, (unsigned)pbt.n);
+  const int rc = tile::dispatch_nb(NB, [&](auto nb) {
+    return tile::launch<skinny_kernel<nb(), TRANS>>(grid, tile::shm_bytes(nb() * 16, AST), st, A, lda,
+                                                    B, ldb, C, ldc, M, K, alpha, beta, part, pbt);
+  });
+  if (rc == tile::kNoSuchNb) return fail(DEIG_EINVAL, "skinny: unsupported N = %d", NB * 16);
+  return rc;
 }
 
 // Split-K factor: enough blocks for ~4 resident per CU (latency hiding: HBM

@@ -368,6 +368,49 @@ def _pad_vector(v, d: int, dp: int, device, name: str):
     return v.contiguous()
 
 
+def _transform_operands(W, d, dp, mean, dev, wname: str):
+    """The W and mean operands of ``project`` and the PCA transforms: ``(W, mean, k)`` with
+    W (checked: 2-D, 1 <= k <= 256, rows matching the samples) zero-padded to dp rows and
+    column-major, mean as ``_pad_vector`` gives it on ``dev``.  d: the number of features
+    when the samples fix it (uint8); None when W's rows do, the samples having dp columns
+    (d itself, or d rounded up to a multiple of 4).  The padding rows and entries are zero:
+    they meet zero columns of the samples."""
+    W = require_device_tensor(W, wname)
+    if W.dim() != 2:
+        raise ValueError(f"{wname} must be 2-D (d, k), got shape {tuple(W.shape)}")
+    rows, k = W.shape
+    if not 1 <= k <= 256:
+        raise ValueError(f"k={k} out of range [1, 256]")
+    if d is None:
+        d = rows
+        if d > dp or (dp != d and dp != (d + 3) // 4 * 4):
+            raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
+    elif rows != d:
+        raise ValueError(f"shape mismatch: X has {d} features, W has {rows} rows")
+    mean = _pad_vector(mean, d, dp, dev, "mean")
+    if dp != d:
+        Wp = torch.zeros((dp, k), dtype=torch.float32, device=W.device)
+        Wp[:d] = W
+        W = Wp
+    return W.t().contiguous().t(), mean, k
+
+
+def _transform_buffers(n: int, k: int, dev, residual: bool, energy: bool):
+    """(Y, res, en): Y (n, k) and, where asked for, the residuals and energies (n,), else None."""
+    return (torch.empty((n, k), dtype=torch.float32, device=dev),
+            torch.empty(n, dtype=torch.float32, device=dev) if residual else None,
+            torch.empty(n, dtype=torch.float32, device=dev) if energy else None)
+
+
+def _transform_result(Y, res, en):
+    """Y, or the tuple (Y[, residual][, energy])."""
+    return Y if res is None and en is None else tuple(t for t in (Y, res, en) if t is not None)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def column_sums_u8(x: torch.Tensor, mode: str = "auto") -> torch.Tensor:
     """sums[j] = sum_r v[r, j] of uint8 samples (include/deig.h deig_colsum_u8): a (d,)
     float64 tensor from an integer accumulation - exact for mode "raw", the integer sum of
@@ -435,39 +478,21 @@ def pca_transform_u8(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None
     with k <= 256.  Centred in double when the bytes are staged, before the product.
     Returns Y, or the tuple (Y[, residual][, energy]) as ``pca_transform``."""
     X, mode, n, d, dp = _u8_samples(X, mode, "pca_transform_u8")
-    W = require_device_tensor(W, "W")
-    if W.dim() != 2:
-        raise ValueError(f"W must be 2-D (d, k), got shape {tuple(W.shape)}")
-    k = W.shape[1]
-    if not 1 <= k <= 256:
-        raise ValueError(f"k={k} out of range [1, 256]")
-    if W.shape[0] != d:
-        raise ValueError(f"shape mismatch: X has {d} features, W has {W.shape[0]} rows")
     dev = X.device
-    mu = _pad_vector(mean, d, dp, dev, "mean")
-    if dp != d:  # zero bytes, zero rows of W, zero mean entries
-        Wp = torch.zeros((dp, k), dtype=torch.float32, device=W.device)
-        Wp[:d] = W
-        W = Wp
-    W = W.to(dev).t().contiguous().t()  # column-major
-    Y = torch.empty((n, k), dtype=torch.float32, device=dev)
-    res = torch.empty(n, dtype=torch.float32, device=dev) if residual else None
-    en = torch.empty(n, dtype=torch.float32, device=dev) if energy else None
+    W, mu, k = _transform_operands(W, d, dp, mean, dev, "W")
+    W = W.to(dev)
+    Y, res, en = _transform_buffers(n, k, dev, residual, energy)
     if n > 0:
         L = _lib.lib()
         with torch.cuda.device(dev):
             nbytes = L.deig_pca_transform_u8_workspace(n, dp, k)
             ws = _workspace(dev, nbytes)
             rc = L.deig_pca_transform_u8(X.data_ptr(), n, dp, X.stride(0), _lib.U8_MODES[mode],
-                                         mu.data_ptr() if mu is not None else None, W.data_ptr(),
-                                         k, _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k),
-                                         res.data_ptr() if residual else None,
-                                         en.data_ptr() if energy else None, ws.data_ptr(), nbytes,
+                                         _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp), Y.data_ptr(),
+                                         _ld(Y, 0, k), _ptr(res), _ptr(en), ws.data_ptr(), nbytes,
                                          _stream(dev))
         _lib.check(rc, "deig_pca_transform_u8")
-    if not residual and not energy:
-        return Y
-    return tuple(t for t in (Y, res, en) if t is not None)
+    return _transform_result(Y, res, en)
 
 
 def sigma_hat_u8(x: torch.Tensor, mode: str = "auto", alpha: float | None = None,
@@ -1024,28 +1049,17 @@ def sym_power(S: torch.Tensor, Q: torch.Tensor, cs: torch.Tensor, steps: int,
 def project(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     """Y = X W  (NB:345 ``X @ matrix_w``): X (n, d) row-major, W (d, k) any layout."""
     X = _rowmajor_4(require_device_tensor(X, "project"), "X")
-    W = require_device_tensor(W, "matrix_w")
-    if W.dim() != 2:
-        raise ValueError(f"matrix_w must be 2-D (d, k), got shape {tuple(W.shape)}")
     n, dp = X.shape
-    d, k = W.shape
-    if not 1 <= k <= 256:
-        raise ValueError(f"k={k} out of range [1, 256]")
-    if d > dp or (dp != d and dp != (d + 3) // 4 * 4):
-        raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
-    if dp != d:
-        Wp = torch.zeros((dp, k), dtype=torch.float32, device=W.device)
-        Wp[:d] = W
-        W = Wp
-    W = W.t().contiguous().t()  # column-major
-    Y = torch.empty((n, k), dtype=torch.float32, device=X.device)
+    dev = X.device
+    W, _, k = _transform_operands(W, None, dp, None, dev, "matrix_w")
+    Y, _, _ = _transform_buffers(n, k, dev, False, False)
     L = _lib.lib()
-    with torch.cuda.device(X.device):
+    with torch.cuda.device(dev):
         nbytes = L.deig_project_workspace(n, dp, k)
-        ws = _workspace(X.device, nbytes)
+        ws = _workspace(dev, nbytes)
         rc = L.deig_project_f32(X.data_ptr(), n, dp, _ld(X, 0, dp), W.data_ptr(), k,
                                 _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k), ws.data_ptr(), nbytes,
-                                _stream(X.device))
+                                _stream(dev))
     _lib.check(rc, "deig_project_f32")
     return Y
 
@@ -1070,47 +1084,21 @@ def pca_transform(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = 
         X = require_device_tensor(X, "pca_transform", keep_f64=True)
         X, mu = (X - mu.to(X.device)).to(torch.float32), None
     X = _rowmajor_4(require_device_tensor(X, "pca_transform"), "X")
-    W = require_device_tensor(W, "W")
-    if W.dim() != 2:
-        raise ValueError(f"W must be 2-D (d, k), got shape {tuple(W.shape)}")
     n, dp = X.shape
-    d, k = W.shape
-    if not 1 <= k <= 256:
-        raise ValueError(f"k={k} out of range [1, 256]")
-    if d > dp or (dp != d and dp != (d + 3) // 4 * 4):
-        raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
-    if mu is not None:
-        if mu.numel() != d:
-            raise ValueError(f"mean must hold d = {d} numbers, got {mu.numel()}")
-        mu = mu.to(X.device)
-    if dp != d:  # zero columns, zero rows of W, zero mean entries
-        Wp = torch.zeros((dp, k), dtype=torch.float32, device=W.device)
-        Wp[:d] = W
-        W = Wp
-        if mu is not None:
-            mu = torch.cat([mu, torch.zeros(dp - d, dtype=torch.float64, device=mu.device)])
-    if mu is not None:
-        mu = mu.contiguous()
-    W = W.t().contiguous().t()  # column-major
     dev = X.device
-    Y = torch.empty((n, k), dtype=torch.float32, device=dev)
-    res = torch.empty(n, dtype=torch.float32, device=dev) if residual else None
-    en = torch.empty(n, dtype=torch.float32, device=dev) if energy else None
+    W, mu, k = _transform_operands(W, None, dp, mu, dev, "W")
+    Y, res, en = _transform_buffers(n, k, dev, residual, energy)
     if n > 0:
         L = _lib.lib()
         with torch.cuda.device(dev):
             nbytes = L.deig_pca_transform_workspace(n, dp, k)
             ws = _workspace(dev, nbytes)
-            rc = L.deig_pca_transform_f32(X.data_ptr(), n, dp, _ld(X, 0, dp),
-                                          mu.data_ptr() if mu is not None else None, W.data_ptr(),
-                                          k, _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k),
-                                          res.data_ptr() if residual else None,
-                                          en.data_ptr() if energy else None, ws.data_ptr(), nbytes,
+            rc = L.deig_pca_transform_f32(X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu),
+                                          W.data_ptr(), k, _ld(W, 1, dp), Y.data_ptr(),
+                                          _ld(Y, 0, k), _ptr(res), _ptr(en), ws.data_ptr(), nbytes,
                                           _stream(dev))
         _lib.check(rc, "deig_pca_transform_f32")
-    if not residual and not energy:
-        return Y
-    return tuple(t for t in (Y, res, en) if t is not None)
+    return _transform_result(Y, res, en)
 
 
 # ---------------------------------------------------------------- building block
