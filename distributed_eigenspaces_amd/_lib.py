@@ -18,172 +18,72 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DEIG_LIB_PATH") or os.path.join(HERE, "libdeig.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "deig.h")
 
-DEIG_OK = 0
-DEIG_NOT_CONVERGED = 1
-DEIG_EINVAL = -1
-DEIG_EHIP = -2
-DEIG_EWORKSPACE = -3
-DEIG_ETIMEOUT = -4
-DEIG_SYRK_AUTO = 0
-DEIG_SYRK_SPLIT3 = 1
-DEIG_SYRK_FP32 = 2
-DEIG_SYRK_ACCUMULATE = 0x100
-SYRK_ALGOS = {"auto": DEIG_SYRK_AUTO, "split3": DEIG_SYRK_SPLIT3, "fp32": DEIG_SYRK_FP32}
-DEIG_SWEEP_AUTO = 0
-DEIG_SWEEP_BF16X6 = 1
-DEIG_SWEEP_FP32 = 2
-DEIG_SWEEP_PREPARED = 0x100
-DEIG_SWEEP_ROUND_Q = 0x200
-DEIG_SWEEP_FAST = 0x400
-DEIG_SWEEP_HALF = 0x1000
-DEIG_SWEEP_KERNEL_ONLY = 0x800
-SWEEP_ALGOS = {"auto": DEIG_SWEEP_AUTO, "bf16x6": DEIG_SWEEP_BF16X6, "fp32": DEIG_SWEEP_FP32}
-DEIG_U8_RAW = 0
-DEIG_U8_GRAY3 = 1
-U8_MODES = {"raw": DEIG_U8_RAW, "gray": DEIG_U8_GRAY3}
-DEIG_F32 = 0
-DEIG_F64 = 1
-DEIG_OJA_AUTO = 0
-DEIG_OJA_TWO_PASS = 1
-DEIG_OJA_RESIDENT = 2
-OJA_ALGOS = {"auto": DEIG_OJA_AUTO, "two_pass": DEIG_OJA_TWO_PASS, "resident": DEIG_OJA_RESIDENT}
-
 
 class SolverOpts(ctypes.Structure):
-    """``deig_solver_opts`` (include/deig.h); build with :func:`solver_opts`."""
+    """``deig_solver_opts`` (include/deig.h); build with :func:`solver_opts`.  Its
+    ``_fields_`` are the header's, set below once the header is parsed."""
 
-    _fields_ = [
-        ("size", ctypes.c_int),
-        ("sweep_algo", ctypes.c_int),
-        ("rr_every", ctypes.c_int),
-        ("chebyshev", ctypes.c_int),
-        ("cheb_above", ctypes.c_float),
-        ("deflate", ctypes.c_int),
-        ("deflate_early", ctypes.c_int),
-        ("jacobi_early_sweeps", ctypes.c_int),
-        ("jacobi_early_above", ctypes.c_float),
-        ("fast_until", ctypes.c_float),
-        ("round_until", ctypes.c_float),
-        ("debug", ctypes.c_int),
-        ("half_until", ctypes.c_float),
-    ]
 
-_c_i64 = ctypes.c_int64
-_c_sz = ctypes.c_size_t
-_vp = ctypes.c_void_p
-_fp = ctypes.c_void_p  # device pointers are passed as integers
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double}
 
-SIGNATURES = {
-    "deig_version": (ctypes.c_int, []),
-    "deig_shutdown": (None, []),
-    "deig_oja_error": (ctypes.c_int, [_vp, _c_sz, _c_i64, _c_i64, ctypes.c_int, _vp]),
-    "deig_last_error": (ctypes.c_char_p, []),
-    "deig_syrk_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_float, _fp, _c_i64,
-                                     _vp, _c_sz, _vp]),
-    "deig_syrk_workspace": (_c_sz, [_c_i64, _c_i64]),
-    "deig_syrk_f32_ex": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_float, _fp,
-                                        _c_i64, ctypes.c_int, _vp, _c_sz, _vp]),
-    "deig_syrk_workspace_ex": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_syrk_u8": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_double,
-                                    _fp, _c_i64, _fp, _c_i64, _vp, _c_sz, _vp]),
-    "deig_syrk_u8_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_default_subspace": (ctypes.c_int, [_c_i64, ctypes.c_int]),
-    "deig_topk_sym_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, _c_i64,
-                                         _fp, _c_i64, _fp, ctypes.POINTER(ctypes.c_int),
-                                         ctypes.POINTER(ctypes.c_float), _vp, _c_sz, _vp]),
-    "deig_topk_workspace": (_c_sz, [_c_i64, ctypes.c_int, ctypes.c_int]),
-    "deig_solver_opts_init": (None, [ctypes.POINTER(SolverOpts)]),
-    "deig_topk_sym_ex": (ctypes.c_int, [_fp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, _c_i64,
-                                        _fp, _c_i64, _fp, ctypes.POINTER(ctypes.c_int),
-                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(SolverOpts),
-                                        _vp, _c_sz, _vp]),
-    "deig_topk_workspace_ex": (_c_sz, [_c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.POINTER(SolverOpts)]),
-    "deig_topk_batch_workspace": (_c_sz, [ctypes.c_int, _c_i64, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.POINTER(SolverOpts)]),
-    "deig_topk_sym_batch": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_int, _c_i64,
-                                           _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_float, ctypes.POINTER(_vp), _c_i64,
-                                           ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int),
-                                           ctypes.POINTER(ctypes.c_float),
-                                           ctypes.POINTER(SolverOpts), _vp, _c_sz,
-                                           ctypes.POINTER(_vp), _vp]),
-    "deig_topk_sym_batch_ex": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_int, _c_i64,
-                                              _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_float, ctypes.POINTER(_vp), _c_i64,
-                                              ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int),
-                                              ctypes.POINTER(ctypes.c_float),
-                                              ctypes.POINTER(ctypes.c_int),
-                                              ctypes.POINTER(SolverOpts), _vp, _c_sz, _vp]),
-    "deig_projavg_topk_ex": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_float,
-                                            ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_float, _fp, ctypes.c_int, _c_i64, _fp,
-                                            _c_i64, _fp, ctypes.POINTER(ctypes.c_int),
-                                            ctypes.POINTER(ctypes.c_float),
-                                            ctypes.POINTER(SolverOpts), _vp, _c_sz, _vp]),
-    "deig_projavg_workspace_ex": (_c_sz, [_c_i64, _c_i64, ctypes.c_int, ctypes.c_int,
-                                          ctypes.POINTER(SolverOpts)]),
-    "deig_syrk_shift": (ctypes.c_int, [_fp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_double,
-                                       _fp, _c_i64, _fp, _c_i64, _vp, _c_sz, _vp]),
-    "deig_syrk_shift_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_colsum": (ctypes.c_int, [_fp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _fp, _vp, _c_sz, _vp]),
-    "deig_colsum_workspace": (_c_sz, [_c_i64, _c_i64]),
-    "deig_syrk_centered": (ctypes.c_int, [_fp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _fp,
-                                          ctypes.c_double, _fp, _c_i64, _fp, _c_i64, _fp, _vp, _c_sz,
-                                          _vp]),
-    "deig_syrk_centered_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_pca_transform_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, _fp, _fp, ctypes.c_int,
-                                              _c_i64, _fp, _c_i64, _fp, _fp, _vp, _c_sz, _vp]),
-    "deig_pca_transform_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_colsum_u8": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp, _vp, _c_sz,
-                                      _vp]),
-    "deig_colsum_u8_workspace": (_c_sz, [_c_i64, _c_i64]),
-    "deig_syrk_u8_centered": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp,
-                                             ctypes.c_double, _fp, _c_i64, _fp, _c_i64, _fp, _vp,
-                                             _c_sz, _vp]),
-    "deig_syrk_u8_centered_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_pca_transform_u8": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp, _fp,
-                                             ctypes.c_int, _c_i64, _fp, _c_i64, _fp, _fp, _vp,
-                                             _c_sz, _vp]),
-    "deig_pca_transform_u8_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_projavg_topk_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_float,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_float, _fp, ctypes.c_int, _c_i64, _fp,
-                                             _c_i64, _fp, ctypes.POINTER(ctypes.c_int),
-                                             ctypes.POINTER(ctypes.c_float), _vp, _c_sz, _vp]),
-    "deig_projavg_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int, ctypes.c_int]),
-    "deig_oja_step_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_float, _fp,
-                                         ctypes.c_int, _c_i64, _vp, _c_sz, _vp]),
-    "deig_oja_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_oja_steps_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_float,
-                                          _fp, ctypes.c_int, _c_i64, ctypes.c_int, _vp, _c_sz,
-                                          _vp]),
-    "deig_oja_steps_ex": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_float,
-                                         _fp, ctypes.c_int, _c_i64, ctypes.c_int, ctypes.c_int, _vp,
-                                         _c_sz, _vp]),
-    "deig_sym_apply_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _fp, ctypes.c_int, _c_i64, _fp,
-                                          _c_i64, ctypes.c_float, ctypes.c_int, _vp, _c_sz, _vp]),
-    "deig_sym_power_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _fp, ctypes.c_int, _c_i64, _fp,
-                                          _c_i64, _fp, ctypes.c_int, ctypes.c_int, _vp, _c_sz,
-                                          _vp]),
-    "deig_sym_apply_workspace": (_c_sz, [_c_i64, ctypes.c_int, ctypes.c_int]),
-    "deig_project_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, _fp, ctypes.c_int, _c_i64,
-                                        _fp, _c_i64, _vp, _c_sz, _vp]),
-    "deig_project_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_gemm_skinny_f32": (ctypes.c_int, [ctypes.c_int, _fp, _c_i64, _fp, _c_i64, _fp, _c_i64,
-                                            _c_i64, _c_i64, _c_i64, ctypes.c_float,
-                                            ctypes.c_float, _vp, _c_sz, _vp]),
-    "deig_gemm_skinny_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "deig_procrustes_avg_f32": (ctypes.c_int, [_fp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _fp, _c_i64,
-                                               ctypes.POINTER(ctypes.c_float), ctypes.c_int, _fp,
-                                               _c_i64, _fp, _fp, _vp, _c_sz, _vp]),
-    "deig_procrustes_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
-    "deig_subspace_dist_f32": (ctypes.c_int, [_fp, _c_i64, _fp, _c_i64, _c_i64, ctypes.c_int, _fp,
-                                              _vp, _c_sz, _vp]),
-    "deig_subspace_dist_workspace": (_c_sz, [_c_i64, ctypes.c_int]),
-}
+
+def _ctype(decl: str, proto: str, ret: bool = False):
+    """ctypes type of one C declaration (a return type, or a parameter with or without its
+    name).  Pointers are c_void_p (device pointers are passed as integers, host ones with
+    byref or as ctypes arrays) except the options struct; an unknown type raises."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        if ret:
+            if words == ["char", "*"]:
+                return ctypes.c_char_p
+        else:
+            return ctypes.POINTER(SolverOpts) if words[0] == "deig_solver_opts" else ctypes.c_void_p
+    elif ret and words == ["void"]:
+        return None
+    elif words and words[0] in _SCALARS and len(words) <= (1 if ret else 2):
+        return _SCALARS[words[0]]
+    raise ValueError(f"include/deig.h: no ctypes type for {decl.strip()!r} in {proto!r}")
+
+
+def parse_header(text: str):
+    """``(prototypes, constants, fields)`` of a deig.h text: ``{name: (restype, [argtypes])}``
+    of every ``deig_*`` function, ``{name: int}`` of every ``#define DEIG_<NAME>`` with an
+    integer value (or another DEIG_ name's), and deig_solver_opts' ``[(field, ctype)]``."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {}
+    for name, val in re.findall(r"^#define[ \t]+(DEIG_[A-Z0-9_]+)[ \t]+"
+                                r"\(?(-?(?:0x[0-9a-fA-F]+|\d+)|DEIG_[A-Z0-9_]+)\)?[ \t]*$", text, re.M):
+        consts[name] = consts[val] if val.startswith("DEIG_") else int(val, 0)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    fields = []
+    struct = re.search(r"typedef struct deig_solver_opts \{(.*?)\} deig_solver_opts;", text, re.S)
+    if struct:
+        fields = [(f.split()[-1], _ctype(f, "deig_solver_opts"))
+                  for f in struct.group(1).split(";") if f.strip()]
+        text = text.replace(struct.group(0), " ")
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s*]*?)\b(deig_[a-z0-9_]+)\s*\(([^()]*)\)\s*;",
+                                      text):
+        proto = f"{' '.join(ret.split())} {name}({' '.join(args.split())})"
+        params = [] if args.strip() in ("", "void") else args.split(",")
+        protos[name] = (_ctype(ret, proto, ret=True), [_ctype(a, proto) for a in params])
+    lost = set(re.findall(r"\b(deig_[a-z0-9_]+)\s*\(", text)) - set(protos)
+    if lost:
+        raise ValueError(f"include/deig.h: cannot parse the prototype of {sorted(lost)}")
+    return protos, consts, fields
+
+
+# The header is the single source: entry-point signatures, DEIG_* constants (module
+# attributes below) and the options struct are all read from it.
+SIGNATURES, _consts, SolverOpts._fields_ = parse_header(open(HEADER).read())
+globals().update(_consts)
+
+# name -> code of the algorithm / mode arguments (the names are Python's)
+SYRK_ALGOS = {"auto": DEIG_SYRK_AUTO, "split3": DEIG_SYRK_SPLIT3, "fp32": DEIG_SYRK_FP32}
+SWEEP_ALGOS = {"auto": DEIG_SWEEP_AUTO, "bf16x6": DEIG_SWEEP_BF16X6, "fp32": DEIG_SWEEP_FP32}
+U8_MODES = {"raw": DEIG_U8_RAW, "gray": DEIG_U8_GRAY3}
+OJA_ALGOS = {"auto": DEIG_OJA_AUTO, "two_pass": DEIG_OJA_TWO_PASS, "resident": DEIG_OJA_RESIDENT}
 
 _lock = threading.Lock()
 _lib = None

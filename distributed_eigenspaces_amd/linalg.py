@@ -59,9 +59,14 @@ class _Workspace(threading.local):
 _ws = _Workspace()
 
 
-def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """Per-thread, per-device, per-stream grow-only uint8 workspace."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+def _stream(device: torch.device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _workspace(device: torch.device, nbytes: int, stream: int | None = None) -> torch.Tensor:
+    """Per-thread, per-device, per-stream grow-only uint8 workspace (stream: the device's
+    current stream, for a caller that has looked it up already)."""
+    key = (device.index, _stream(device) if stream is None else stream)
     buf = _ws.bufs.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
@@ -69,8 +74,18 @@ def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
     return buf
 
 
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+def _call(device: torch.device, name: str, args: tuple, query: str, qargs: tuple) -> int:
+    """The one call path of the entry points that end in ``(ws, ws_bytes, stream)``: on
+    ``device``, size the workspace with ``query(*qargs)``, take this thread's cached buffer
+    (never NULL; what an earlier call left in it stays when it is large enough), call
+    ``name(*args, ws, ws_bytes, stream)`` on the current stream and map the return code
+    (``_lib.check``).  Returns the code (DEIG_OK or DEIG_NOT_CONVERGED)."""
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        nbytes = getattr(L, query)(*qargs)
+        stream = _stream(device)
+        rc = getattr(L, name)(*args, _workspace(device, nbytes, stream).data_ptr(), nbytes, stream)
+    return _lib.check(rc, name)
 
 
 def require_device_tensor(t, name: str = "input", keep_f64: bool = False) -> torch.Tensor:
@@ -100,13 +115,22 @@ def _rowmajor_4(t: torch.Tensor, name: str) -> torch.Tensor:
         raise ValueError(f"{name} must be 2-D, got shape {tuple(t.shape)}")
     ok = (t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1]
           and t.shape[1] % 4 == 0 and t.data_ptr() % 16 == 0)
-    if ok:
-        return t
-    d = t.shape[1]
-    dp = (d + 3) // 4 * 4
+    return t if ok else _pad_cols(t, (t.shape[1] + 3) // 4 * 4)
+
+
+def _pad_cols(t: torch.Tensor, dp: int) -> torch.Tensor:
+    """A fresh contiguous float32 copy of the 2-D ``t`` with its columns zero-padded to dp."""
     out = torch.zeros((t.shape[0], dp), dtype=torch.float32, device=t.device)
-    out[:, :d] = t
+    out[:, :t.shape[1]] = t
     return out
+
+
+def _stack_4(Wt: torch.Tensor, dp: int) -> torch.Tensor:
+    """The (m k) x d stack of bases as the servers read it: dp columns, unit column stride,
+    row stride % 4 == 0, 16-byte aligned (a zero-padded copy where it is not)."""
+    if dp != Wt.shape[1] or Wt.stride(1) != 1 or Wt.stride(0) % 4 or Wt.data_ptr() % 16:
+        Wt = _pad_cols(Wt, dp)
+    return Wt
 
 
 def _ld(t: torch.Tensor, dim: int, extent: int) -> int:
@@ -115,6 +139,47 @@ def _ld(t: torch.Tensor, dim: int, extent: int) -> int:
     stride (``(1, 1)`` for a ``(d, 1)`` tensor, whatever its layout): there is no second
     row or column, so the extent itself describes the same memory."""
     return int(extent) if t.shape[dim] == 1 else t.stride(dim)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _check_k(k, d: int) -> int:
+    k = int(k)
+    if not 1 <= k <= d:
+        raise ValueError(f"k={k} out of range [1, {d}]")
+    return k
+
+
+def _elem_type(dtype: torch.dtype) -> int:
+    """The library's element-type code of a float32 / float64 operand."""
+    return _lib.DEIG_F64 if dtype == torch.float64 else _lib.DEIG_F32
+
+
+def _check_result_dtype(dtype: torch.dtype) -> None:
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype must be torch.float32 or torch.float64")
+
+
+def _alpha(alpha, n: int) -> float:
+    return (1.0 / n) if alpha is None else float(alpha)
+
+
+def _nan_cov(d: int, dtype: torch.dtype, device, with_mean: bool = False):
+    """The covariance of n = 0 samples (numpy: zeros / 0 -> NaN, with a RuntimeWarning; that
+    value is kept): a (d, d) NaN tensor, with_mean: also the (d,) float64 NaN mean."""
+    S = torch.full((d, d), float("nan"), dtype=dtype, device=device)
+    return (S, torch.full((d,), float("nan"), dtype=torch.float64, device=device)) \
+        if with_mean else S
+
+
+def _cov_outputs(S: torch.Tensor, ld: int, f64_first: bool) -> tuple:
+    """The two output slots of a covariance entry point, ``(S64, lds64, S, lds)`` for float
+    samples (f64_first) and ``(S, lds, S64, lds64)`` for uint8 ones: ``S`` in the slot of
+    its dtype, NULL in the other."""
+    mine, null = (S.data_ptr(), ld), (None, ld)
+    return mine + null if (S.dtype == torch.float64) == f64_first else null + mine
 
 
 def default_subspace(d: int, k: int) -> int:
@@ -167,9 +232,7 @@ def sigma_hat(x: torch.Tensor, alpha: float | None = None,
         raise ValueError(f"x must be 2-D (n, d), got {tuple(x.shape)}")
     n, d = x.shape
     if n == 0:
-        # numpy: zeros / 0 -> NaN (with a RuntimeWarning); keep that behaviour
-        return torch.full((d, d), float("nan"), dtype=torch.float32, device=x.device)
-    a = (1.0 / n) if alpha is None else float(alpha)
+        return _nan_cov(d, torch.float32, x.device)
     xx = _rowmajor_4(x, "x")
     dp = xx.shape[1]
     if out is not None and dp == d and out.shape == (d, d) and out.is_contiguous() \
@@ -177,15 +240,9 @@ def sigma_hat(x: torch.Tensor, alpha: float | None = None,
         S = out
     else:
         S = torch.empty((dp, dp), dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_syrk_workspace_ex(n, dp, code)
-        ws = _workspace(x.device, nbytes) if nbytes else None
-        rc = L.deig_syrk_f32_ex(xx.data_ptr(), n, dp, xx.stride(0), ctypes.c_float(a),
-                                S.data_ptr(), S.stride(0), code,
-                                ws.data_ptr() if ws is not None else None, nbytes,
-                                _stream(x.device))
-    _lib.check(rc, "deig_syrk_f32_ex")
+    _call(x.device, "deig_syrk_f32_ex",
+          (xx.data_ptr(), n, dp, xx.stride(0), _alpha(alpha, n), S.data_ptr(), S.stride(0), code),
+          "deig_syrk_workspace_ex", (n, dp, code))
     if dp != d:
         S = S[:d, :d].contiguous()
         if out is not None:
@@ -203,32 +260,16 @@ def sigma_hat_shift(x: torch.Tensor, alpha: float | None = None,
     relative to the centred data instead of the dominant mean direction of an
     uncentered covariance.  Returns a (d, d) tensor of ``dtype`` (float64: the
     reference's), bit-exactly symmetric."""
-    if not isinstance(x, torch.Tensor):
-        x = torch.as_tensor(x)
-    if x.dtype not in (torch.float32, torch.float64):
-        x = x.to(torch.float64)
-    x = require_device_tensor(x, "sigma_hat_shift", keep_f64=True)
-    if x.dim() != 2:
-        raise ValueError(f"x must be 2-D (n, d), got {tuple(x.shape)}")
-    if dtype not in (torch.float32, torch.float64):
-        raise ValueError("dtype must be torch.float32 or torch.float64")
+    x = _float_samples(x, "sigma_hat_shift")
+    _check_result_dtype(dtype)
     n, d = x.shape
     if n == 0:
-        return torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
-    if x.stride(1) != 1 or x.stride(0) < d:
-        x = x.contiguous()
-    a = (1.0 / n) if alpha is None else float(alpha)
-    xtype = _lib.DEIG_F64 if x.dtype == torch.float64 else _lib.DEIG_F32
+        return _nan_cov(d, dtype, x.device)
+    xtype = _elem_type(x.dtype)
     S = torch.empty((d, d), dtype=dtype, device=x.device)
-    f64 = dtype == torch.float64
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_syrk_shift_workspace(n, d, xtype)
-        ws = _workspace(x.device, nbytes)
-        rc = L.deig_syrk_shift(x.data_ptr(), xtype, n, d, x.stride(0), ctypes.c_double(a),
-                               S.data_ptr() if f64 else None, d, None if f64 else S.data_ptr(), d,
-                               ws.data_ptr(), nbytes, _stream(x.device))
-    _lib.check(rc, "deig_syrk_shift")
+    _call(x.device, "deig_syrk_shift",
+          (x.data_ptr(), xtype, n, d, x.stride(0), _alpha(alpha, n), *_cov_outputs(S, d, True)),
+          "deig_syrk_shift_workspace", (n, d, xtype))
     if out is not None:
         out.copy_(S)
         return out
@@ -259,14 +300,9 @@ def column_sums(x: torch.Tensor) -> torch.Tensor:
     sums = torch.zeros(d, dtype=torch.float64, device=x.device)
     if n == 0 or d == 0:
         return sums
-    xtype = _lib.DEIG_F64 if x.dtype == torch.float64 else _lib.DEIG_F32
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_colsum_workspace(n, d)
-        ws = _workspace(x.device, nbytes)
-        rc = L.deig_colsum(x.data_ptr(), xtype, n, d, _ld(x, 0, d), sums.data_ptr(), ws.data_ptr(),
-                           nbytes, _stream(x.device))
-    _lib.check(rc, "deig_colsum")
+    _call(x.device, "deig_colsum",
+          (x.data_ptr(), _elem_type(x.dtype), n, d, _ld(x, 0, d), sums.data_ptr()),
+          "deig_colsum_workspace", (n, d))
     return sums
 
 
@@ -283,33 +319,22 @@ def sigma_hat_centered(x: torch.Tensor, center: torch.Tensor | None = None,
     ((d,) float64)."""
     x = _float_samples(x, "sigma_hat_centered")
     dtype = dtype or torch.float64
-    if dtype not in (torch.float32, torch.float64):
-        raise ValueError("dtype must be torch.float32 or torch.float64")
+    _check_result_dtype(dtype)
     n, d = x.shape
     if n == 0:
-        S = torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
-        return (S, torch.full((d,), float("nan"), dtype=torch.float64, device=x.device)) \
-            if return_mean else S
+        return _nan_cov(d, dtype, x.device, return_mean)
     c = None
     if center is not None:
         c = torch.as_tensor(center).to(device=x.device, dtype=torch.float64).contiguous()
         if c.shape != (d,):
             raise ValueError(f"center must have shape ({d},), got {tuple(c.shape)}")
-    a = (1.0 / n) if alpha is None else float(alpha)
-    xtype = _lib.DEIG_F64 if x.dtype == torch.float64 else _lib.DEIG_F32
+    xtype = _elem_type(x.dtype)
     S = torch.empty((d, d), dtype=dtype, device=x.device)
     mean = torch.empty(d, dtype=torch.float64, device=x.device) if return_mean else None
-    f64 = dtype == torch.float64
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_syrk_centered_workspace(n, d, xtype)
-        ws = _workspace(x.device, nbytes)
-        rc = L.deig_syrk_centered(x.data_ptr(), xtype, n, d, _ld(x, 0, d),
-                                  c.data_ptr() if c is not None else None, ctypes.c_double(a),
-                                  S.data_ptr() if f64 else None, d, None if f64 else S.data_ptr(), d,
-                                  mean.data_ptr() if mean is not None else None, ws.data_ptr(),
-                                  nbytes, _stream(x.device))
-    _lib.check(rc, "deig_syrk_centered")
+    _call(x.device, "deig_syrk_centered",
+          (x.data_ptr(), xtype, n, d, _ld(x, 0, d), _ptr(c), _alpha(alpha, n),
+           *_cov_outputs(S, d, True), _ptr(mean)),
+          "deig_syrk_centered_workspace", (n, d, xtype))
     return (S, mean) if return_mean else S
 
 
@@ -407,10 +432,6 @@ def _transform_result(Y, res, en):
     return Y if res is None and en is None else tuple(t for t in (Y, res, en) if t is not None)
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def column_sums_u8(x: torch.Tensor, mode: str = "auto") -> torch.Tensor:
     """sums[j] = sum_r v[r, j] of uint8 samples (include/deig.h deig_colsum_u8): a (d,)
     float64 tensor from an integer accumulation - exact for mode "raw", the integer sum of
@@ -420,13 +441,9 @@ def column_sums_u8(x: torch.Tensor, mode: str = "auto") -> torch.Tensor:
     sums = torch.zeros(dp, dtype=torch.float64, device=x.device)
     if n == 0 or d == 0:
         return sums[:d]
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_colsum_u8_workspace(n, dp)
-        ws = _workspace(x.device, nbytes)
-        rc = L.deig_colsum_u8(x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode], sums.data_ptr(),
-                              ws.data_ptr(), nbytes, _stream(x.device))
-    _lib.check(rc, "deig_colsum_u8")
+    _call(x.device, "deig_colsum_u8",
+          (x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode], sums.data_ptr()),
+          "deig_colsum_u8_workspace", (n, dp))
     return sums[:d].contiguous() if dp != d else sums
 
 
@@ -442,28 +459,16 @@ def sigma_hat_u8_centered(x: torch.Tensor, center: torch.Tensor | None = None, m
     (float64 by default; float32 is its rounding), bit-exactly symmetric; with
     ``return_mean`` also the shard's own mean ((d,) float64)."""
     x, mode, n, d, dp = _u8_samples(x, mode, "sigma_hat_u8_centered")
-    if dtype not in (torch.float32, torch.float64):
-        raise ValueError("dtype must be torch.float32 or torch.float64")
+    _check_result_dtype(dtype)
     if n == 0:
-        S = torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
-        return (S, torch.full((d,), float("nan"), dtype=torch.float64, device=x.device)) \
-            if return_mean else S
+        return _nan_cov(d, dtype, x.device, return_mean)
     c = _pad_vector(center, d, dp, x.device, "center")
-    a = (1.0 / n) if alpha is None else float(alpha)
     S = torch.empty((dp, dp), dtype=dtype, device=x.device)
     mean = torch.empty(dp, dtype=torch.float64, device=x.device) if return_mean else None
-    f32 = dtype == torch.float32
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_syrk_u8_centered_workspace(n, dp, _lib.U8_MODES[mode])
-        ws = _workspace(x.device, nbytes)
-        rc = L.deig_syrk_u8_centered(x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode],
-                                     c.data_ptr() if c is not None else None, ctypes.c_double(a),
-                                     S.data_ptr() if f32 else None, dp,
-                                     None if f32 else S.data_ptr(), dp,
-                                     mean.data_ptr() if mean is not None else None, ws.data_ptr(),
-                                     nbytes, _stream(x.device))
-    _lib.check(rc, "deig_syrk_u8_centered")
+    _call(x.device, "deig_syrk_u8_centered",
+          (x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode], _ptr(c), _alpha(alpha, n),
+           *_cov_outputs(S, dp, False), _ptr(mean)),
+          "deig_syrk_u8_centered_workspace", (n, dp, _lib.U8_MODES[mode]))
     if dp != d:
         S = S[:d, :d].contiguous()
         mean = mean[:d].contiguous() if mean is not None else None
@@ -483,15 +488,10 @@ def pca_transform_u8(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None
     W = W.to(dev)
     Y, res, en = _transform_buffers(n, k, dev, residual, energy)
     if n > 0:
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            nbytes = L.deig_pca_transform_u8_workspace(n, dp, k)
-            ws = _workspace(dev, nbytes)
-            rc = L.deig_pca_transform_u8(X.data_ptr(), n, dp, X.stride(0), _lib.U8_MODES[mode],
-                                         _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp), Y.data_ptr(),
-                                         _ld(Y, 0, k), _ptr(res), _ptr(en), ws.data_ptr(), nbytes,
-                                         _stream(dev))
-        _lib.check(rc, "deig_pca_transform_u8")
+        _call(dev, "deig_pca_transform_u8",
+              (X.data_ptr(), n, dp, X.stride(0), _lib.U8_MODES[mode], _ptr(mu), W.data_ptr(), k,
+               _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k), _ptr(res), _ptr(en)),
+              "deig_pca_transform_u8_workspace", (n, dp, k))
     return _transform_result(Y, res, en)
 
 
@@ -512,23 +512,15 @@ def sigma_hat_u8(x: torch.Tensor, mode: str = "auto", alpha: float | None = None
     """
     x, mode, n, d, dp = _u8_samples(x, mode, "sigma_hat_u8")
     if n == 0:
-        return torch.full((d, d), float("nan"), dtype=dtype, device=x.device)
-    a = (1.0 / n) if alpha is None else float(alpha)
-    if dtype not in (torch.float32, torch.float64):
-        raise ValueError("dtype must be torch.float32 or torch.float64")
+        return _nan_cov(d, dtype, x.device)
+    _check_result_dtype(dtype)
     direct = (out is not None and dp == d and out.dtype == dtype and out.device == x.device
               and out.shape == (d, d) and out.stride(1) == 1 and out.stride(0) >= d)
     S = out if direct else torch.empty((dp, dp), dtype=dtype, device=x.device)
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        nbytes = L.deig_syrk_u8_workspace(n, dp, _lib.U8_MODES[mode])
-        ws = _workspace(x.device, nbytes)
-        f32 = dtype == torch.float32
-        lds = S.stride(0)
-        rc = L.deig_syrk_u8(x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode], ctypes.c_double(a),
-                            S.data_ptr() if f32 else None, lds, None if f32 else S.data_ptr(), lds,
-                            ws.data_ptr(), nbytes, _stream(x.device))
-    _lib.check(rc, "deig_syrk_u8")
+    _call(x.device, "deig_syrk_u8",
+          (x.data_ptr(), n, dp, x.stride(0), _lib.U8_MODES[mode], _alpha(alpha, n),
+           *_cov_outputs(S, S.stride(0), False)),
+          "deig_syrk_u8_workspace", (n, dp, _lib.U8_MODES[mode]))
     if direct:  # written in place
         return out
     if dp != d:
@@ -545,7 +537,8 @@ def _pad_dim(d: int) -> int:
 
 
 def _finish(rc, V, evals, sweeps, resid, what):
-    _lib.check(rc, what)
+    """The EigResult of a solve that returned ``rc`` (checked); called by the public op
+    itself, so that the warning points at the op's caller."""
     conv = rc == _lib.DEIG_OK
     if not conv:
         warnings.warn(f"{what}: {_lib.last_error()}", _lib.NotConvergedWarning, stacklevel=3)
@@ -555,6 +548,12 @@ def _finish(rc, V, evals, sweeps, resid, what):
 
 def _colmajor(d: int, k: int, device) -> torch.Tensor:
     return torch.empty((k, d), dtype=torch.float32, device=device).t()
+
+
+def _solver_outputs(d: int, k: int, device):
+    """(V, evals, sweeps, resid): the device outputs of one solve and its host out-words."""
+    return (_colmajor(d, k, device), torch.empty(k, dtype=torch.float32, device=device),
+            ctypes.c_int(0), ctypes.c_float(0))
 
 
 def _warm(q0, d, device):
@@ -604,28 +603,19 @@ def topk_eigh(S: torch.Tensor, k: int, *, p: int | None = None, tol: float = DEF
     if S.dim() != 2 or S.shape[0] != S.shape[1]:
         raise ValueError(f"expected a square matrix, got {tuple(S.shape)}")
     d = S.shape[0]
-    k = int(k)
-    if not 1 <= k <= d:
-        raise ValueError(f"k={k} out of range [1, {d}]")
+    k = _check_k(k, d)
     if check_finite and not bool(torch.isfinite(S).all()):
         raise ValueError("array must not contain infs or NaNs")
     S = _solver_matrix(S)
     q, k0, ldq = _warm(q0, d, S.device)
     pp = int(p) if p else 0
-    stype = _lib.DEIG_F64 if S.dtype == torch.float64 else _lib.DEIG_F32
-    o = opts if opts is not None else _lib.solver_opts()
-    V = _colmajor(d, k, S.device)
-    evals = torch.empty(k, dtype=torch.float32, device=S.device)
-    sweeps, resid = ctypes.c_int(0), ctypes.c_float(0)
-    L = _lib.lib()
-    with torch.cuda.device(S.device):
-        nbytes = L.deig_topk_workspace_ex(d, k, pp, stype, ctypes.byref(o))
-        ws = _workspace(S.device, nbytes)
-        rc = L.deig_topk_sym_ex(S.data_ptr(), stype, d, S.stride(0), k, pp, int(max_sweeps),
-                                ctypes.c_float(tol), q.data_ptr() if q is not None else None,
-                                k0, ldq, V.data_ptr(), d, evals.data_ptr(),
-                                ctypes.byref(sweeps), ctypes.byref(resid), ctypes.byref(o),
-                                ws.data_ptr(), nbytes, _stream(S.device))
+    stype = _elem_type(S.dtype)
+    o = ctypes.byref(opts if opts is not None else _lib.solver_opts())
+    V, evals, sweeps, resid = _solver_outputs(d, k, S.device)
+    rc = _call(S.device, "deig_topk_sym_ex",
+               (S.data_ptr(), stype, d, S.stride(0), k, pp, int(max_sweeps), tol, _ptr(q), k0, ldq,
+                V.data_ptr(), d, evals.data_ptr(), ctypes.byref(sweeps), ctypes.byref(resid), o),
+               "deig_topk_workspace_ex", (d, k, pp, stype, o))
     return _finish(rc, V, evals, sweeps, resid, "deig_topk_sym_ex")
 
 
@@ -651,9 +641,7 @@ def topk_eigh_batch(Ss, k: int, *, p: int | None = None, tol: float = DEFAULT_TO
             raise ValueError("topk_eigh_batch: every matrix must have the same shape, dtype, device")
         if check_finite and not bool(torch.isfinite(S).all()):
             raise ValueError("array must not contain infs or NaNs")
-    k = int(k)
-    if not 1 <= k <= d:
-        raise ValueError(f"k={k} out of range [1, {d}]")
+    k = _check_k(k, d)
     mats = [_solver_matrix(S) for S in Ss]
     lds = mats[0].stride(0)
     if any(S.stride(0) != lds for S in mats):
@@ -661,26 +649,19 @@ def topk_eigh_batch(Ss, k: int, *, p: int | None = None, tol: float = DEFAULT_TO
         lds = d
     W = len(mats)
     pp = int(p) if p else 0
-    stype = _lib.DEIG_F64 if dt == torch.float64 else _lib.DEIG_F32
-    o = opts if opts is not None else _lib.solver_opts()
+    stype = _elem_type(dt)
+    o = ctypes.byref(opts if opts is not None else _lib.solver_opts())
     Vs = [_colmajor(d, k, dev) for _ in range(W)]
     evs = [torch.empty(k, dtype=torch.float32, device=dev) for _ in range(W)]
     sweeps = (ctypes.c_int * W)()
     resid = (ctypes.c_float * W)()
     status = (ctypes.c_int * W)()
-    vp = ctypes.c_void_p
-    S_arr = (vp * W)(*[S.data_ptr() for S in mats])
-    V_arr = (vp * W)(*[V.data_ptr() for V in Vs])
-    E_arr = (vp * W)(*[e.data_ptr() for e in evs])
-    cur = torch.cuda.current_stream(dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nbytes = L.deig_topk_batch_workspace(W, d, k, pp, stype, ctypes.byref(o))
-        ws = _workspace(dev, nbytes)
-        rc = L.deig_topk_sym_batch_ex(W, S_arr, stype, d, lds, k, pp, int(max_sweeps),
-                                      ctypes.c_float(tol), V_arr, d, E_arr, sweeps, resid, status,
-                                      ctypes.byref(o), ws.data_ptr(), nbytes, cur.cuda_stream)
-    _lib.check(rc, "deig_topk_sym_batch_ex")
+    S_arr, V_arr, E_arr = ((ctypes.c_void_p * W)(*[t.data_ptr() for t in ts])
+                           for ts in (mats, Vs, evs))
+    rc = _call(dev, "deig_topk_sym_batch_ex",
+               (W, S_arr, stype, d, lds, k, pp, int(max_sweeps), tol, V_arr, d, E_arr, sweeps,
+                resid, status, o),
+               "deig_topk_batch_workspace", (W, d, k, pp, stype, o))
     if rc != _lib.DEIG_OK:
         warnings.warn(f"deig_topk_sym_batch_ex: {_lib.last_error()}", _lib.NotConvergedWarning,
                       stacklevel=2)
@@ -710,36 +691,24 @@ def projavg_topk(Wt: torch.Tensor, k: int, scale: float, *, p: int | None = None
     if Wt.dim() != 2:
         raise ValueError("Wt must be 2-D ((m k) x d)")
     mk, d = Wt.shape
-    k = int(k)
-    if not 1 <= k <= d:
-        raise ValueError(f"k={k} out of range [1, {d}]")
+    k = _check_k(k, d)
     dp = _pad_dim(d)
     if not p:
         dp = max(dp, default_subspace(max(dp, (min(k, MAX_P) + 15) // 16 * 16), k))
-    if dp != d or Wt.stride(1) != 1 or Wt.stride(0) % 4 or Wt.data_ptr() % 16:
-        Wp = torch.zeros((mk, dp), dtype=torch.float32, device=Wt.device)
-        Wp[:, :d] = Wt
-        Wt = Wp
+    Wt = _stack_4(Wt, dp)
     q, k0, ldq = _warm(q0, d, Wt.device)
     if q is not None and dp != d:
         qp = torch.zeros((dp, k0), dtype=torch.float32, device=Wt.device)
         qp[:d] = q
         q, ldq = qp.t().contiguous().t(), dp
     pp = int(p) if p else default_subspace(dp, k)
-    o = opts if opts is not None else _lib.solver_opts()
-    V = _colmajor(dp, k, Wt.device)
-    evals = torch.empty(k, dtype=torch.float32, device=Wt.device)
-    sweeps, resid = ctypes.c_int(0), ctypes.c_float(0)
-    L = _lib.lib()
-    with torch.cuda.device(Wt.device):
-        nbytes = L.deig_projavg_workspace_ex(dp, mk, k, pp, ctypes.byref(o))
-        ws = _workspace(Wt.device, nbytes)
-        rc = L.deig_projavg_topk_ex(Wt.data_ptr(), dp, mk, Wt.stride(0), ctypes.c_float(scale),
-                                    k, pp, int(max_sweeps), ctypes.c_float(tol),
-                                    q.data_ptr() if q is not None else None, k0, ldq,
-                                    V.data_ptr(), dp, evals.data_ptr(), ctypes.byref(sweeps),
-                                    ctypes.byref(resid), ctypes.byref(o), ws.data_ptr(), nbytes,
-                                    _stream(Wt.device))
+    o = ctypes.byref(opts if opts is not None else _lib.solver_opts())
+    V, evals, sweeps, resid = _solver_outputs(dp, k, Wt.device)
+    rc = _call(Wt.device, "deig_projavg_topk_ex",
+               (Wt.data_ptr(), dp, mk, Wt.stride(0), scale, k, pp, int(max_sweeps), tol, _ptr(q),
+                k0, ldq, V.data_ptr(), dp, evals.data_ptr(), ctypes.byref(sweeps),
+                ctypes.byref(resid), o),
+               "deig_projavg_workspace_ex", (dp, mk, k, pp, o))
     res = _finish(rc, V, evals, sweeps, resid, "deig_projavg_topk_ex")
     if dp != d:
         res.V = res.V[:d].t().contiguous().t()
@@ -784,9 +753,7 @@ def procrustes_average(Wt: torch.Tensor, k: int, *, ref=None, weights=None,
     if Wt.dim() != 2:
         raise ValueError("Wt must be 2-D ((m k) x d)")
     mk, d = Wt.shape
-    k = int(k)
-    if not 1 <= k <= d:
-        raise ValueError(f"k={k} out of range [1, {d}]")
+    k = _check_k(k, d)
     if k > MAX_P:
         raise ValueError(f"procrustes_average takes k <= {MAX_P}; use projavg_topk above")
     if mk < k or mk % k:
@@ -794,10 +761,7 @@ def procrustes_average(Wt: torch.Tensor, k: int, *, ref=None, weights=None,
     m = mk // k
     dev = Wt.device
     dp = _pad_dim(d)
-    if dp != d or Wt.stride(1) != 1 or Wt.stride(0) % 4 or Wt.data_ptr() % 16:
-        Wp = torch.zeros((mk, dp), dtype=torch.float32, device=dev)
-        Wp[:, :d] = Wt
-        Wt = Wp
+    Wt = _stack_4(Wt, dp)
     rptr, ldref, rkeep = None, dp, None
     if ref is not None:
         if isinstance(ref, int):
@@ -819,14 +783,10 @@ def procrustes_average(Wt: torch.Tensor, k: int, *, ref=None, weights=None,
     V = _colmajor(dp, k, dev)
     Z = torch.empty((m, k, k), dtype=torch.float32, device=dev)
     cos = torch.empty((m, k), dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nbytes = L.deig_procrustes_workspace(dp, mk, k)
-        ws = _workspace(dev, nbytes)
-        rc = L.deig_procrustes_avg_f32(Wt.data_ptr(), dp, mk, Wt.stride(0), k, rptr, ldref, wptr,
-                                       int(iters), V.data_ptr(), dp, Z.data_ptr(), cos.data_ptr(),
-                                       ws.data_ptr(), nbytes, _stream(dev))
-    _lib.check(rc, "deig_procrustes_avg_f32")
+    _call(dev, "deig_procrustes_avg_f32",
+          (Wt.data_ptr(), dp, mk, Wt.stride(0), k, rptr, ldref, wptr, int(iters), V.data_ptr(), dp,
+           Z.data_ptr(), cos.data_ptr()),
+          "deig_procrustes_workspace", (dp, mk, k))
     if dp != d:
         V = V[:d].t().contiguous().t()
     return ProcrustesResult(V=V, cosines=cos, Z=Z)
@@ -848,13 +808,9 @@ def subspace_distance(A: torch.Tensor, B: torch.Tensor):
     Ac = _colmajor_basis(A, d, k, dp, dev, "A")
     Bc = _colmajor_basis(B, d, k, dp, dev, "B")
     out = torch.empty(2, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nbytes = L.deig_subspace_dist_workspace(dp, k)
-        ws = _workspace(dev, nbytes)
-        rc = L.deig_subspace_dist_f32(Ac.data_ptr(), Ac.stride(1), Bc.data_ptr(), Bc.stride(1), dp,
-                                      k, out.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
-    _lib.check(rc, "deig_subspace_dist_f32")
+    _call(dev, "deig_subspace_dist_f32",
+          (Ac.data_ptr(), Ac.stride(1), Bc.data_ptr(), Bc.stride(1), dp, k, out.data_ptr()),
+          "deig_subspace_dist_workspace", (dp, k))
     fro, two = out.tolist()
     return fro, two
 
@@ -874,20 +830,21 @@ def oja_step(Xb: torch.Tensor, V: torch.Tensor, eta: float) -> torch.Tensor:
     """
     Xb = _rowmajor_4(require_device_tensor(Xb, "oja_step"), "Xb")
     b, d = Xb.shape
-    if V.dim() != 2 or V.shape[0] != d or V.stride(0) != 1 or V.dtype != torch.float32 \
-            or V.device != Xb.device:
-        raise ValueError("V must be a (d, k) column-major float32 tensor on Xb's device")
-    k = V.shape[1]
-    L = _lib.lib()
-    with torch.cuda.device(Xb.device):
-        nbytes = L.deig_oja_workspace(b, d, k)
-        ws = _workspace(Xb.device, nbytes)
-        rc = L.deig_oja_step_f32(Xb.data_ptr(), b, d, Xb.stride(0), ctypes.c_float(eta),
-                                 V.data_ptr(), k, _ld(V, 1, d), ws.data_ptr(), nbytes,
-                                 _stream(Xb.device))
-    _lib.check(rc, "deig_oja_step_f32")
+    k = _oja_basis(V, Xb, "Xb")
+    _call(Xb.device, "deig_oja_step_f32",
+          (Xb.data_ptr(), b, d, Xb.stride(0), eta, V.data_ptr(), k, _ld(V, 1, d)),
+          "deig_oja_workspace", (b, d, k))
     oja_check(Xb.device, b, d, k)
     return V
+
+
+def _oja_basis(V: torch.Tensor, X: torch.Tensor, xname: str) -> int:
+    """Check Oja's basis against the samples X (named ``xname``): (d, k) column-major
+    float32 on X's device.  Returns k."""
+    if V.dim() != 2 or V.shape[0] != X.shape[1] or V.stride(0) != 1 or V.dtype != torch.float32 \
+            or V.device != X.device:
+        raise ValueError(f"V must be a (d, k) column-major float32 tensor on {xname}'s device")
+    return V.shape[1]
 
 
 def oja_check(device, b: int, d: int, k: int) -> None:
@@ -922,18 +879,11 @@ def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
     nb = n // b if b > 0 else 0
     if nb < 1:
         raise ValueError(f"need at least one full batch of {batch} rows, got {n} rows")
-    if V.dim() != 2 or V.shape[0] != d or V.stride(0) != 1 or V.dtype != torch.float32 \
-            or V.device != X.device:
-        raise ValueError("V must be a (d, k) column-major float32 tensor on X's device")
-    k = V.shape[1]
-    L = _lib.lib()
-    with torch.cuda.device(X.device):
-        nbytes = L.deig_oja_workspace(b, d, k)
-        ws = _workspace(X.device, nbytes)
-        rc = L.deig_oja_steps_ex(X.data_ptr(), nb, b, d, X.stride(0), ctypes.c_float(eta),
-                                 V.data_ptr(), k, _ld(V, 1, d), int(orth_every),
-                                 _lib.OJA_ALGOS[algo], ws.data_ptr(), nbytes, _stream(X.device))
-    _lib.check(rc, "deig_oja_steps_ex")
+    k = _oja_basis(V, X, "X")
+    _call(X.device, "deig_oja_steps_ex",
+          (X.data_ptr(), nb, b, d, X.stride(0), eta, V.data_ptr(), k, _ld(V, 1, d), int(orth_every),
+           _lib.OJA_ALGOS[algo]),
+          "deig_oja_workspace", (b, d, k))
     if check:
         oja_check(X.device, b, d, k)
     return V
@@ -962,21 +912,40 @@ def sym_apply(S: torch.Tensor, Q: torch.Tensor, algo: str = "auto", alpha: float
     round_q = round_q or fast
     if algo not in _lib.SWEEP_ALGOS:
         raise ValueError(f"algo must be one of {sorted(_lib.SWEEP_ALGOS)}, got {algo!r}")
-    S = require_device_tensor(S, "sym_apply")
-    Q = require_device_tensor(Q, "Q")
-    d = S.shape[0]
-    if S.dim() != 2 or S.shape[1] != d or Q.dim() != 2 or Q.shape[0] != d:
-        raise ValueError(f"shape mismatch: S {tuple(S.shape)}, Q {tuple(Q.shape)}")
-    p = Q.shape[1]
-    if d % 4 or S.stride(1) != 1 or S.stride(0) % 4 or S.data_ptr() % 16:
-        raise ValueError("S must be row-major with d % 4 == 0 and a 16-byte aligned, %4 stride")
+    S, Q, d, p = _sweep_operands(S, Q, "sym_apply")
     if round_q:
         if algo == "fp32" or not Q.is_contiguous() or Q.dtype != torch.float32:
             raise ValueError("round_q needs algo bf16x6/auto and a contiguous float32 Q "
                              "(it is rounded in place)")
     Q = Q.contiguous()
     Y = out if out is not None else torch.empty((d, p), dtype=torch.float32, device=S.device)
-    code = _lib.SWEEP_ALGOS[algo]
+    code = _sweep_code(_lib.SWEEP_ALGOS[algo], prepared, round_q, fast, half)
+    if kernel_only:
+        if code & 0xff == _lib.DEIG_SWEEP_FP32:
+            raise ValueError("kernel_only needs algo bf16x6/auto")
+        code |= _lib.DEIG_SWEEP_KERNEL_ONLY | _lib.DEIG_SWEEP_PREPARED
+    _call(S.device, "deig_sym_apply_f32",
+          (S.data_ptr(), d, S.stride(0), Q.data_ptr(), p, Q.stride(0), Y.data_ptr(), Y.stride(0),
+           alpha, code),
+          "deig_sym_apply_workspace", (d, p, code))
+    return Y
+
+
+def _sweep_operands(S, Q, name: str):
+    """``(S, Q, d, p)``: the operands of a sweep on the device, S checked as the kernels
+    read it (square, row-major, d % 4 == 0, aligned) and Q as d x p."""
+    S = require_device_tensor(S, name)
+    Q = require_device_tensor(Q, "Q")
+    d = S.shape[0]
+    if S.dim() != 2 or S.shape[1] != d or Q.dim() != 2 or Q.shape[0] != d:
+        raise ValueError(f"shape mismatch: S {tuple(S.shape)}, Q {tuple(Q.shape)}")
+    if d % 4 or S.stride(1) != 1 or S.stride(0) % 4 or S.data_ptr() % 16:
+        raise ValueError("S must be row-major with d % 4 == 0 and a 16-byte aligned, %4 stride")
+    return S, Q, d, Q.shape[1]
+
+
+def _sweep_code(code: int, prepared: bool, round_q: bool, fast: bool, half: bool) -> int:
+    """The algorithm ``code`` with the DEIG_SWEEP_* flag bits of a sweep's mode."""
     if prepared and code != _lib.DEIG_SWEEP_FP32:
         code |= _lib.DEIG_SWEEP_PREPARED
     if round_q:
@@ -985,19 +954,7 @@ def sym_apply(S: torch.Tensor, Q: torch.Tensor, algo: str = "auto", alpha: float
         code |= _lib.DEIG_SWEEP_FAST
     if half:
         code |= _lib.DEIG_SWEEP_HALF
-    if kernel_only:
-        if code & 0xff == _lib.DEIG_SWEEP_FP32:
-            raise ValueError("kernel_only needs algo bf16x6/auto")
-        code |= _lib.DEIG_SWEEP_KERNEL_ONLY | _lib.DEIG_SWEEP_PREPARED
-    L = _lib.lib()
-    with torch.cuda.device(S.device):
-        nbytes = L.deig_sym_apply_workspace(d, p, code)
-        ws = _workspace(S.device, nbytes)
-        rc = L.deig_sym_apply_f32(S.data_ptr(), d, S.stride(0), Q.data_ptr(), p, Q.stride(0),
-                                  Y.data_ptr(), Y.stride(0), ctypes.c_float(alpha), code,
-                                  ws.data_ptr(), nbytes, _stream(S.device))
-    _lib.check(rc, "deig_sym_apply_f32")
-    return Y
+    return code
 
 
 def sym_power(S: torch.Tensor, Q: torch.Tensor, cs: torch.Tensor, steps: int,
@@ -1011,37 +968,18 @@ def sym_power(S: torch.Tensor, Q: torch.Tensor, cs: torch.Tensor, steps: int,
     Flags as for ``sym_apply`` (bf16x6 only)."""
     fast = fast or half
     round_q = round_q or fast
-    S = require_device_tensor(S, "sym_power")
-    Q = require_device_tensor(Q, "Q")
-    d = S.shape[0]
-    if S.dim() != 2 or S.shape[1] != d or Q.dim() != 2 or Q.shape[0] != d:
-        raise ValueError(f"shape mismatch: S {tuple(S.shape)}, Q {tuple(Q.shape)}")
-    p = Q.shape[1]
-    if d % 4 or S.stride(1) != 1 or S.stride(0) % 4 or S.data_ptr() % 16:
-        raise ValueError("S must be row-major with d % 4 == 0 and a 16-byte aligned, %4 stride")
+    S, Q, d, p = _sweep_operands(S, Q, "sym_power")
     if not Q.is_contiguous() or Q.dtype != torch.float32:
         raise ValueError("Q must be a contiguous float32 tensor (updated in place)")
     cs = cs.to(device=S.device, dtype=torch.float32).contiguous()
     if cs.numel() != p:
         raise ValueError(f"cs must hold p = {p} column scales")
     Y = out if out is not None else torch.empty((d, p), dtype=torch.float32, device=S.device)
-    code = _lib.DEIG_SWEEP_BF16X6
-    if prepared:
-        code |= _lib.DEIG_SWEEP_PREPARED
-    if round_q:
-        code |= _lib.DEIG_SWEEP_ROUND_Q
-    if fast:
-        code |= _lib.DEIG_SWEEP_FAST
-    if half:
-        code |= _lib.DEIG_SWEEP_HALF
-    L = _lib.lib()
-    with torch.cuda.device(S.device):
-        nbytes = L.deig_sym_apply_workspace(d, p, code)
-        ws = _workspace(S.device, nbytes)
-        rc = L.deig_sym_power_f32(S.data_ptr(), d, S.stride(0), Q.data_ptr(), p, Q.stride(0),
-                                  Y.data_ptr(), Y.stride(0), cs.data_ptr(), int(steps), code,
-                                  ws.data_ptr(), nbytes, _stream(S.device))
-    _lib.check(rc, "deig_sym_power_f32")
+    code = _sweep_code(_lib.DEIG_SWEEP_BF16X6, prepared, round_q, fast, half)
+    _call(S.device, "deig_sym_power_f32",
+          (S.data_ptr(), d, S.stride(0), Q.data_ptr(), p, Q.stride(0), Y.data_ptr(), Y.stride(0),
+           cs.data_ptr(), int(steps), code),
+          "deig_sym_apply_workspace", (d, p, code))
     return Y
 
 
@@ -1053,14 +991,10 @@ def project(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     dev = X.device
     W, _, k = _transform_operands(W, None, dp, None, dev, "matrix_w")
     Y, _, _ = _transform_buffers(n, k, dev, False, False)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        nbytes = L.deig_project_workspace(n, dp, k)
-        ws = _workspace(dev, nbytes)
-        rc = L.deig_project_f32(X.data_ptr(), n, dp, _ld(X, 0, dp), W.data_ptr(), k,
-                                _ld(W, 1, dp), Y.data_ptr(), _ld(Y, 0, k), ws.data_ptr(), nbytes,
-                                _stream(dev))
-    _lib.check(rc, "deig_project_f32")
+    _call(dev, "deig_project_f32",
+          (X.data_ptr(), n, dp, _ld(X, 0, dp), W.data_ptr(), k, _ld(W, 1, dp), Y.data_ptr(),
+           _ld(Y, 0, k)),
+          "deig_project_workspace", (n, dp, k))
     return Y
 
 
@@ -1089,15 +1023,10 @@ def pca_transform(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = 
     W, mu, k = _transform_operands(W, None, dp, mu, dev, "W")
     Y, res, en = _transform_buffers(n, k, dev, residual, energy)
     if n > 0:
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            nbytes = L.deig_pca_transform_workspace(n, dp, k)
-            ws = _workspace(dev, nbytes)
-            rc = L.deig_pca_transform_f32(X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu),
-                                          W.data_ptr(), k, _ld(W, 1, dp), Y.data_ptr(),
-                                          _ld(Y, 0, k), _ptr(res), _ptr(en), ws.data_ptr(), nbytes,
-                                          _stream(dev))
-        _lib.check(rc, "deig_pca_transform_f32")
+        _call(dev, "deig_pca_transform_f32",
+              (X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp),
+               Y.data_ptr(), _ld(Y, 0, k), _ptr(res), _ptr(en)),
+              "deig_pca_transform_workspace", (n, dp, k))
     return _transform_result(Y, res, en)
 
 
@@ -1130,13 +1059,8 @@ def gemm_skinny(A: torch.Tensor, B: torch.Tensor, trans_a: bool, alpha: float = 
             or C.dtype != torch.float32 or C.device != A.device or C.stride(1) != 1:
         raise ValueError(f"C must be a ({M}, {N}) float32 tensor on A's device with unit "
                          "column stride")
-    L = _lib.lib()
-    with torch.cuda.device(A.device):
-        nbytes = L.deig_gemm_skinny_workspace(M, N, K)
-        ws = _workspace(A.device, nbytes)
-        rc = L.deig_gemm_skinny_f32(int(trans_a), A.data_ptr(), _ld(A, 0, A.shape[1]),
-                                    B.data_ptr(), _ld(B, 0, N), C.data_ptr(), _ld(C, 0, N), M, N,
-                                    K, ctypes.c_float(alpha), ctypes.c_float(beta), ws.data_ptr(),
-                                    nbytes, _stream(A.device))
-    _lib.check(rc, "deig_gemm_skinny_f32")
+    _call(A.device, "deig_gemm_skinny_f32",
+          (int(trans_a), A.data_ptr(), _ld(A, 0, A.shape[1]), B.data_ptr(), _ld(B, 0, N),
+           C.data_ptr(), _ld(C, 0, N), M, N, K, alpha, beta),
+          "deig_gemm_skinny_workspace", (M, N, K))
     return C

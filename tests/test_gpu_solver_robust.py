@@ -9,6 +9,7 @@ relative against float64 eigh of the same fp32 matrix; where it does not (gap
 0.99, a residual floor at the fp32 level is ~1e-2 of the gap), the solver must
 either converge or say so (NotConvergedWarning) - never return a wrong basis as
 converged."""
+import os
 import warnings
 
 import numpy as np
@@ -74,9 +75,12 @@ def test_stall_is_reported(cuda):
     from distributed_eigenspaces_amd import _lib
     d, k = 512, 8
     S = _matrix(_flat_tail(d, k, 0.999), seed=6)
-    with pytest.warns(_lib.NotConvergedWarning):
+    with pytest.warns(_lib.NotConvergedWarning) as rec:
         r = de.topk_eigh(torch.from_numpy(S).to(cuda), k, max_sweeps=60)
     assert not r.converged and r.resid > 1e-6
+    # attributed to the line that called the public op, not to the binding layer
+    mine = [w for w in rec if issubclass(w.category, _lib.NotConvergedWarning)]
+    assert [os.path.realpath(w.filename) for w in mine] == [os.path.realpath(__file__)]
 
 
 def test_chebyshev_keeps_spiked_sweep_counts(cuda):
