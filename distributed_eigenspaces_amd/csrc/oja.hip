@@ -10,6 +10,7 @@
 // each workgroup's block of Xb held in registers - Xb read once per batch.
 #include <algorithm>
 
+#include "bf16_split.hpp"
 #include "deig_internal.hpp"
 
 namespace deig {
@@ -135,16 +136,6 @@ __global__ __launch_bounds__(64) void chol_rinv_kernel(const float* __restrict__
 // bf16 operands for the split products of the NN pass (as the covariance and the
 // sweeps: x = hi + lo, three bf16 MFMA products hi hi + hi lo + lo hi per fp32
 // product, exact products summed in fp32: ~2^-16 relative).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t cvt2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-__device__ __forceinline__ float lo_f(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
-
 // 8 fp32 -> (hi, lo) bf16x8 pairs.
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
   const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};

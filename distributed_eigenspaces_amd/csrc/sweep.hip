@@ -23,26 +23,13 @@
 // order (deterministic), fused with the solver's basis step (sweep_finish_kernel).
 #include <type_traits>
 
+#include "bf16_split.hpp"
 #include "deig_internal.hpp"
 
 namespace deig {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SW_KS = 64;  // k per sweep step (two 32-deep MFMA k-groups)
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Two fp32 -> packed bf16 (element 0 in the low half), round to nearest even;
-// one v_cvt_pk_bf16_f32 (NaN stays NaN).
-__device__ __forceinline__ uint32_t cvt2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-__device__ __forceinline__ float lo_f(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
 
 // 8 consecutive fp32 values -> packed bf16 h, m, l MFMA operands (x = h + m + l).
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& mi,

@@ -29,6 +29,7 @@
 // panel is fetched from HBM once and re-read by the other ~T/nt tiles from
 // L2 / Infinity Cache.
 #include "deig_internal.hpp"
+#include "lds_dma.hpp"
 
 namespace deig {
 namespace {
@@ -69,32 +70,6 @@ __device__ __forceinline__ int64_t block_of(int64_t pos, int64_t Wr, int G) {
   return ((pos + 1) * (int64_t)G + Wr - 1) / Wr - 1;
 }
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// Raw buffer descriptor (gfx950): base, stride 0, num_records bytes, dword format.
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, int nrec) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  i32x4 r;
-  r[0] = (int)(uint32_t)a;
-  r[1] = (int)((uint32_t)(a >> 32) & 0xffffu);
-  r[2] = nrec;
-  r[3] = 0x00020000;
-  return r;
-}
-
-// buffer_load_dwordx4 ... lds: 16 B per lane into LDS at (m0 + 16 * lane).
-// Issued from inline asm on purpose: hipcc cannot tell which LDS bytes an
-// LDS-DMA writes and would otherwise put vmcnt(0) in front of every ds_read of
-// the *other* buffer, serialising the prefetch with the MFMA loop.  The only
-// wait on these loads is the explicit vmcnt(0) before the K-tile barrier.
-__device__ __forceinline__ void dma16(i32x4 rsrc, int voff, const float* lds_dst) {
-  const unsigned m0v = (unsigned)(uintptr_t)(lds_void*)lds_dst;
-  asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-               :
-               : "v"(voff), "s"(rsrc), "s"(m0v)
-               : "memory", "m0");
-}
-
 // DMA the two 256-column panels of K-tile kt into LDS.  One buffer descriptor
 // per K-tile (SGPRs) whose range ends after the last valid row, so rows >= n and
 // the over-read past the end of X return 0.  Only the lane offset lives in a
@@ -105,7 +80,7 @@ __device__ __forceinline__ void stage(const Sched& s, int64_t kt, int i0, int j0
   const int64_t r0 = kt * BK;
   int64_t rows = s.n - r0;
   rows = rows < BK ? rows : BK;
-  const i32x4 rsrc = make_rsrc(s.X + r0 * s.ldx, (int)(rows * s.ldx * 4));
+  const i32x4 rsrc = make_rsrc(s.X + r0 * s.ldx, (uint32_t)(rows * s.ldx * 4));
   int l16 = lane16;
   asm volatile("" : "+v"(l16));
 #pragma unroll
@@ -118,7 +93,7 @@ __device__ __forceinline__ void stage(const Sched& s, int64_t kt, int i0, int j0
 }
 
 __device__ __forceinline__ void kt_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
 }
 

@@ -36,31 +36,29 @@
 //   diag_corr_kernel  S[i][i] += alpha * sum lo_i^2.
 // Tile order: compact XCD groups where G = 256 and nt % 8 == 0
 // (tile_order_compact_kernel), else 8 x 4 super-tiles of the lower triangle, so the
-// ~32 tiles an XCD runs concurrently share few panels in its L2.  Work decomposition (no
-// atomics): q = T / G full phases of one tile per block; the R = T mod G
-// remainder tiles are cut into nseg equal K segments run K-synchronously
-// (segment-major item order) and summed in segment order by syrks_reduce.
+// ~32 tiles an XCD runs concurrently share few panels in its L2.
+// The two persistent kernels differ only in how a K-tile reaches LDS and how the MFMA
+// phases are ordered (segment, segment_h); around the K loop both are the same, each
+// piece stated once:
+//  work_item    the schedule (no atomics): q = T / G full phases of one tile per block;
+//               the R = T mod G remainder tiles are cut into nseg equal K segments run
+//               K-synchronously (segment-major item order) and summed in segment order
+//               by syrks_reduce.  One WorkItem = tile, K range, slab slot, pacing sequence;
+//  pace_point   the item's PaceSeq: every pace_kt K-tiles the XCD's blocks (and every
+//               other time all blocks) wait for each other;
+//  tile_ctx / finish_tile   the wave's place in the tile and its slab; after the K loop
+//               the flushed sums are added back and the tile goes to S or to its slab;
+//  run_pass     (host) pacing counters, kernel, syrks_reduce, diag_corr - once for the
+//               fused path, once per row chunk above it.
 #include <cmath>
 #include <cstdlib>
 
+#include "bf16_split.hpp"
 #include "deig_internal.hpp"
+#include "lds_dma.hpp"
 
 namespace deig {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Two fp32 -> packed bf16 (element 0 in the low half), round to nearest even:
-// one v_cvt_pk_bf16_f32.
-__device__ __forceinline__ uint32_t cvt2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-__device__ __forceinline__ float lo_f(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
 
 constexpr int BT = 256;                      // tile edge (features)
 constexpr int ROWS_PAD = 32;                 // chunk rows are padded to this (2 k-steps)
@@ -75,7 +73,7 @@ constexpr int BLOCK_B = 8 * SLICE_B;         // one panel of a 32-row block: 32 
 constexpr size_t DEFAULT_CHUNK_BYTES = size_t(64) << 30;
 
 struct SSched {
-  const unsigned char* XP;  // bf16 image of this chunk
+  unsigned char* XP;  // bf16 image of this chunk (split_kernel writes, syrks_h_kernel reads)
   float* S;
   float* part;   // one slab per remainder item
   float* accs;   // 1 flush slab per block
@@ -132,24 +130,129 @@ __device__ __noinline__ void xcd_pace(unsigned* ctr, unsigned target) {
   }
 }
 
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, uint32_t nrec) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  i32x4 r;
-  r[0] = (int)(uint32_t)a;
-  r[1] = (int)((uint32_t)(a >> 32) & 0xffffu);
-  r[2] = (int)nrec;
-  r[3] = 0x00020000;
-  return r;
+// Blocks of XCD b & 7 in a grid of G (round-robin dispatch).
+__device__ __forceinline__ unsigned xcd_blocks(const SSched& s) {
+  const int xcd = blockIdx.x & 7;
+  return (unsigned)((s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0));
 }
 
-// 16 B per lane HBM -> LDS at m0 + 16 * lane (see syrk.hip for why inline asm).
-__device__ __forceinline__ void dma16(i32x4 rsrc, int voff, const void* lds_dst) {
-  const unsigned m0v = (unsigned)(uintptr_t)(lds_void*)lds_dst;
-  asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-               :
-               : "v"(voff), "s"(rsrc), "s"(m0v)
-               : "memory", "m0");
+// Pacing points of one work item: every pace_kt K-tiles, n times (n = 0: none); point j
+// (1..n) waits for the XCD's counter to reach base + j * mult.
+struct PaceSeq {
+  int n;
+  unsigned base, mult;
+  unsigned gbase = 0;  // the chip-wide counter's target before this item
+  unsigned gmult = 0;  // blocks that pace chip-wide with this one (G, or a round's items)
+  bool g = false;      // every kChipPaceEvery-th point is also chip-wide
+};
+
+// Where a block stands in its item's PaceSeq; pace_point is called once per K-tile.
+struct PaceState {
+  int since = 0, left, gcount = 0;
+  unsigned target, gtarget;
+  __device__ __forceinline__ explicit PaceState(const PaceSeq& pc)
+      : left(pc.n), target(pc.base), gtarget(pc.gbase) {}
+};
+
+__device__ __forceinline__ void pace_point(const SSched& s, const PaceSeq& pc, PaceState& p) {
+  if (p.left > 0 && ++p.since == s.pace_kt) {
+    p.since = 0;
+    --p.left;
+    p.target += pc.mult;
+    if (threadIdx.x == 0) xcd_pace(s.pace + 32 * (blockIdx.x & 7), p.target);
+    if (pc.g && ++p.gcount == kChipPaceEvery) {  // ... and every other one chip-wide
+      p.gcount = 0;
+      p.gtarget += pc.gmult;
+      if (threadIdx.x == 0) xcd_pace(s.pace + 32 * 8, p.gtarget);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- work items
+// Both persistent kernels run the same schedule.  Full phases (w < q): block L runs all
+// K of tile w G + L, in lock-step with the rest.  Remainder: R tiles x nseg equal K
+// segments, item i = seg * R + r, taken by logical block i mod G in round i / G; its
+// partial sum goes to slab i.  Segment-major numbering keeps the items that run together
+// (and, by the XCD-aware relabel, the ~G/8 on one XCD) on the same K rows of neighbouring
+// tiles, so their panels are shared in L2 rather than each item streaming its own K range
+// from HBM.
+
+// Blocks of this block's XCD (logical L) that run a remainder item in round u: item
+// i = L + u G (the XCD's blocks are logical [L - b/8, + nx)).
+__device__ __forceinline__ int rem_active(const SSched& s, int L, int u) {
+  const int nx = (int)xcd_blocks(s);
+  const int left = s.R * s.nseg - u * s.G - (L - (int)(blockIdx.x >> 3));
+  return left < 0 ? 0 : (left < nx ? left : nx);
+}
+
+__device__ __forceinline__ int rem_rounds(const SSched& s, int L) {
+  const int items = s.R * s.nseg;
+  return L < items ? (items - 1 - L) / s.G + 1 : 0;
+}
+
+// Round u's item of block L: tile index, slot (= segment * R + r) and segment.
+__device__ __forceinline__ void rem_item(const SSched& s, int L, int u, int& tile, int& slot, int& sg) {
+  const int i = L + u * s.G;
+  sg = i / s.R;
+  const int r = i - sg * s.R;
+  tile = s.q * s.G + r;
+  slot = sg * s.R + r;
+}
+
+struct WorkItem {
+  int tile, slot, seg;  // index into s.order; remainder slab and K segment (0 in full phases)
+  int64_t k0, k1;       // K-tiles [k0, k1)
+  bool partial;         // a remainder item: the sum goes to slab `slot`, not to S
+  PaceSeq pc;
+};
+
+// Work item w (< q + rem_rounds) of logical block L, with its pacing sequence.
+// Full phases: every block runs P = NK / pace_kt points per tile, so phase w's point j
+// (1..P) waits for (w P + j) nx arrivals of the XCD's nx blocks: PaceSeq{P, w P nx, nx}.
+// (A running arrival index w P + j times nx, counted through the phases without a bound
+// per item, gives the same targets: a full phase's NK K-tiles hold exactly P points.)
+// The kernels differ in one thing, HALF (syrks_h_kernel) against the fused syrks_kernel:
+// HALF also paces every kChipPaceEvery-th point chip-wide (all G blocks) and paces the
+// remainder items - Pm points per item, Pm from the shortest segment, so every item of a
+// round runs the same count and the targets stay exact across rounds: XCD-wide against
+// the XCD's blocks active in the round, chip-wide against the round's item count.  The
+// fused kernel paces its full phases at the XCD level only (remainder: n = 0).
+template <bool HALF>
+__device__ __forceinline__ WorkItem work_item(const SSched& s, int L, int w) {
+  WorkItem it{0, 0, 0, 0, s.NK, w >= s.q, PaceSeq{0, 0u, 0u}};
+  const unsigned nx = xcd_blocks(s);
+  const unsigned P = s.pace_kt > 0 ? (unsigned)(s.NK / s.pace_kt) : 0u;
+  if (!it.partial) {
+    it.tile = w * s.G + L;
+    it.pc = PaceSeq{(int)P, (unsigned)w * P * nx, nx};
+    if (HALF) {
+      it.pc.g = true;
+      it.pc.gbase = (unsigned)w * (P / kChipPaceEvery) * (unsigned)s.G;
+      it.pc.gmult = (unsigned)s.G;
+    }
+    return it;
+  }
+  const int u = w - s.q;
+  rem_item(s, L, u, it.tile, it.slot, it.seg);
+  // (64-bit divisions run on the VALU: pin the bounds to SGPRs, the DMA descriptors
+  // built from them must be wave-uniform)
+  it.k0 = __builtin_amdgcn_readfirstlane((int)(s.NK * it.seg / s.nseg));
+  it.k1 = __builtin_amdgcn_readfirstlane((int)(s.NK * (it.seg + 1) / s.nseg));
+  const int Pm = (HALF && s.pace_kt > 0 && s.nseg > 0) ? (int)(s.NK / s.nseg / s.pace_kt) : 0;
+  if (Pm > 0) {
+    const int items = s.R * s.nseg;
+    unsigned before = 0;  // arrivals of the earlier rounds: XCD-wide, chip-wide
+    unsigned gb = (unsigned)s.q * (P / kChipPaceEvery) * (unsigned)s.G;
+    for (int v = 0; v < u; ++v) {
+      before += (unsigned)rem_active(s, L, v);
+      gb += (unsigned)min(s.G, items - v * s.G) * (unsigned)(Pm / kChipPaceEvery);
+    }
+    it.pc = PaceSeq{Pm, (unsigned)s.q * P * nx + before * (unsigned)Pm, (unsigned)rem_active(s, L, u)};
+    it.pc.g = true;
+    it.pc.gbase = gb;
+    it.pc.gmult = (unsigned)min(s.G, items - u * s.G);
+  }
+  return it;
 }
 
 // LDS ring geometry: a K-tile is 32 rows; a panel's K-tile is its 8 (octet, hi|lo)
@@ -223,11 +326,6 @@ __device__ __forceinline__ void convert_x(unsigned char* buf, int wave, int lane
       *reinterpret_cast<u32x4*>(R + f * 16) = hv;
       *reinterpret_cast<u32x4*>(R + SLICE_B + f * 16) = lv;
     }
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // ---------------------------------------------------------------- accumulators
@@ -395,31 +493,74 @@ __device__ __forceinline__ void store4(const SSched& s, int ib, int j, bool diag
   }
 }
 
+// A wave's place in its block's tile, and the slab the block flushes into (full phases:
+// the block's own) or leaves its partial sum in (remainder items: the item's).
+struct TileCtx {
+  int lane, wave, wi, wj;  // wave tile: rows 128 wi, columns 64 wj of the tile
+  int ti, tj, i0, j0;      // tile coordinates, in tiles and in features
+  bool diag;
+  float* slab;
+};
+
+__device__ __forceinline__ TileCtx tile_ctx(const SSched& s, const WorkItem& it) {
+  TileCtx c;
+  c.lane = threadIdx.x & 63;
+  c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  c.wi = c.wave >> 2;
+  c.wj = c.wave & 3;
+  const int tt = __builtin_amdgcn_readfirstlane(s.order[it.tile]);
+  c.ti = tt & 0xffff;
+  c.tj = tt >> 16;
+  c.i0 = c.ti * BT;
+  c.j0 = c.tj * BT;
+  c.diag = (c.ti == c.tj);
+  c.slab = it.partial ? s.part + (int64_t)it.slot * SLAB : s.accs + (int64_t)blockIdx.x * SLAB;
+  return c;
+}
+
+// After the K loop: add back what was flushed, then leave the wave's 32 quads in the
+// item's slab (remainder) or store them to S.  IDLE: a wave whose block lies wholly above
+// the diagonal holds zeros - it never flushed and stores nothing to S, but still writes
+// its part of a partial slab (the reduce kernel reads the whole slab).
+// The context comes by value: through a reference the stores to S might alias it, and
+// every store4 then forms its addresses anew with full 64-bit multiplies.
+template <bool IDLE = false>
+__device__ __forceinline__ void finish_tile(const SSched& s, const TileCtx c, Acc& acc, bool flushed,
+                                            bool partial) {
+  if constexpr (!IDLE)
+    if (flushed) unflush(c.slab, acc, c.wave, c.lane);
+  if (partial) {
+#pragma unroll
+    for (int q = 0; q < NQUAD; ++q)
+      *slab_at(c.slab, c.wave, q, c.lane) = f32x4{acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
+    return;
+  }
+  if constexpr (IDLE) return;
+#pragma unroll
+  for (int q = 0; q < NQUAD; ++q) {
+    const float a[4] = {acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
+    store4(s, c.i0 + 128 * c.wi + Acc::qrow(q, c.lane), c.j0 + 64 * c.wj + Acc::qcol(q, c.lane), c.diag, a);
+  }
+}
+
 // One work item of the fused kernel: K-tiles [k0, k1) of a tile on a two-stage ring.
 template <bool SQ>
-__device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int tile, int64_t k0, int64_t k1,
-                        int slot, bool partial, int pace_j, int cseg) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wi = wave >> 2, wj = wave & 3;
-  const int lane16 = lane * 16;
-  const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
-  const int ti = tt & 0xffff, tj = tt >> 16;
-  const int i0 = ti * BT, j0 = tj * BT;
-  const bool diag = (ti == tj);
+__device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, const WorkItem& it) {
+  const TileCtx tc = tile_ctx(s, it);
+  const int lane = tc.lane, wave = tc.wave, wi = tc.wi, wj = tc.wj;
+  const int64_t k0 = it.k0;
+  float* const slab = tc.slab;
   // fused split: this wave's panel origin, valid features in it, DMA lane offset
-  const int fx0 = (wave >= 4 && !diag) ? j0 : i0;
+  const int fx0 = (wave >= 4 && !tc.diag) ? tc.j0 : tc.i0;
   const int fv = s.d - fx0;
-  const int xvoff = 4 * lane < fv ? lane16 : (1 << 30);
+  const int xvoff = 4 * lane < fv ? lane * 16 : (1 << 30);
   // lo^2 of the diagonal: panel A's octets (waves 0-3) of diagonal tiles
-  const bool sqw = SQ;
   float sq[4] = {0.f, 0.f, 0.f, 0.f};
 
   Acc acc;
   acc.zero();
-  float* slab = partial ? s.part + (int64_t)slot * SLAB : s.accs + (int64_t)blockIdx.x * SLAB;
   bool flushed = false;
-  const int64_t nkt = k1 - k0;
+  const int64_t nkt = it.k1 - k0;
   if (nkt > 0) {
     // Nothing else may be in flight on the VM counter while the ring runs (the
     // counted waits assume only DMAs): drain the previous segment's stores.
@@ -433,16 +574,10 @@ __device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int
     wait_vm<0>();
     const int64_t rv0 = s.nrows - (k0 * 32 + 8 * (wave & 3));
     convert_x<SQ>(lds, wave, lane, rv0 < 0 ? 0 : rv0 > 8 ? 8 : (int)rv0, fv, sq);
-    int cur = 0, nxt = 1, since = 0, since_pace = 0;
-    // pacing target: blocks on this XCD x arrival index
-    const int xcd = blockIdx.x & 7;
-    const unsigned nx = (unsigned)((s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0));
+    int cur = 0, nxt = 1, since = 0;
+    PaceState pace(it.pc);
     for (int64_t t = 0; t < nkt; ++t) {
-      if (pace_j >= 0 && ++since_pace == s.pace_kt) {
-        since_pace = 0;
-        ++pace_j;
-        if (threadIdx.x == 0) xcd_pace(s.pace + 32 * xcd, (unsigned)pace_j * nx);
-      }
+      pace_point(s, it.pc, pace);
       // RAW: every wave split its own region of stage t last iteration (its
       // ds_writes retire at the lgkmcnt wait), so the barrier publishes stage t.
       // WAR: stage t-1's ds_reads retired (lgkmcnt) before the barrier, so its
@@ -472,58 +607,13 @@ __device__ __forceinline__ void segment(const SSched& s, unsigned char* lds, int
       nxt = nxt + 1 == 2 ? 0 : nxt + 1;
     }
   }
-  if (flushed) unflush(slab, acc, wave, lane);
-  if (sqw) {  // [segment][octet wave][dp]; summed by diag_corr_kernel
-    float* c = s.corr + (int64_t)(cseg * 4 + wave) * s.dp + i0;
+  if (SQ) {  // [segment][octet wave][dp]; summed by diag_corr_kernel
+    float* c = s.corr + (int64_t)(it.seg * 4 + wave) * s.dp + tc.i0;
 #pragma unroll
     for (int h = 0; h < 2; ++h)
       *reinterpret_cast<f32x2*>(c + 128 * h + 2 * lane) = f32x2{sq[2 * h], sq[2 * h + 1]};
   }
-
-  if (partial) {
-#pragma unroll
-    for (int q = 0; q < NQUAD; ++q)
-      *slab_at(slab, wave, q, lane) = f32x4{acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    return;
-  }
-#pragma unroll
-  for (int q = 0; q < NQUAD; ++q) {
-    const float a[4] = {acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    store4(s, i0 + 128 * wi + Acc::qrow(q, lane), j0 + 64 * wj + Acc::qcol(q, lane), diag, a);
-  }
-}
-
-// Pacing points of one segment: point j (1..n) waits for the XCD counter to reach
-// base + j * mult (n = 0: none).
-struct PaceSeq {
-  int n;
-  unsigned base, mult;
-  unsigned gbase = 0;  // the chip-wide counter's target before this segment
-  unsigned gmult = 0;  // blocks that pace chip-wide with this one (G, or a round's items)
-  bool g = false;      // every kChipPaceEvery-th point is also chip-wide
-};
-
-// Blocks of this block's XCD (logical L) that run a remainder item in round u: item
-// i = L + u G (the XCD's blocks are logical [L - b/8, + nx)).
-__device__ __forceinline__ int rem_active(const SSched& s, int L, int u) {
-  const int xcd = blockIdx.x & 7;
-  const int nx = (s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0);
-  const int left = s.R * s.nseg - u * s.G - (L - (int)(blockIdx.x >> 3));
-  return left < 0 ? 0 : (left < nx ? left : nx);
-}
-
-__device__ __forceinline__ int rem_rounds(const SSched& s, int L) {
-  const int items = s.R * s.nseg;
-  return L < items ? (items - 1 - L) / s.G + 1 : 0;
-}
-
-// Round u's item of block L: tile index, slot (= segment * R + r) and segment.
-__device__ __forceinline__ void rem_item(const SSched& s, int L, int u, int& tile, int& slot, int& sg) {
-  const int i = L + u * s.G;
-  sg = i / s.R;
-  const int r = i - sg * s.R;
-  tile = s.q * s.G + r;
-  slot = sg * s.R + r;
+  finish_tile(s, tc, acc, flushed, it.partial);
 }
 
 // ------------------------------------------------ half-refill ring (d > kFusedMaxD)
@@ -567,25 +657,20 @@ constexpr bool dw_col(int dw, int nb) { return !dw_skip(dw, 7, nb); }  // B bloc
 constexpr bool dw_idle(int dw) { return !dw_row(dw, 7); }
 
 template <int DW>
-__device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, int tile, int64_t k0,
-                                          int64_t k1, int slot, bool partial, const PaceSeq& pc) {
+__device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, const WorkItem& it) {
   constexpr bool idle = dw_idle(DW);
   constexpr bool dgb = DW != kDwOff;  // B operands from the A quarters
   constexpr int QB = 8 * 1024;  // one A quarter
   constexpr int BOFF = 4 * QB;  // the B panel
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wi = wave >> 2, wj = wave & 3;
+  const TileCtx tc = tile_ctx(s, it);
+  const int lane = tc.lane, wave = tc.wave, wi = tc.wi, wj = tc.wj, ti = tc.ti, tj = tc.tj;
   const bool lag = wave >= 4;
-  const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
-  const int ti = tt & 0xffff, tj = tt >> 16;
-  const int i0 = ti * BT, j0 = tj * BT;
-  const bool diag = (ti == tj);
+  const int64_t k0 = it.k0;
+  float* const slab = tc.slab;
   Acc acc;
   acc.zero();
-  float* slab = partial ? s.part + (int64_t)slot * SLAB : s.accs + (int64_t)blockIdx.x * SLAB;
   bool flushed = false;
-  const int64_t nkt = k1 - k0;
+  const int64_t nkt = it.k1 - k0;
   auto bar = [&]() {  // raw barrier; nothing moves across it
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -637,10 +722,7 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
     // so the eight XCDs' slab bursts fall at different K-tiles instead of all at once
     // (each partial sum still spans flush_kt K-tiles, the first one of a segment fewer).
     int since = kFlushStaggerDiv > 0 ? xcd * (s.flush_kt / kFlushStaggerDiv) : 0;
-    int since_pace = 0, pace_left = pc.n;
-    unsigned pace_t = pc.base;
-    int gcount = 0;
-    unsigned gtarget = pc.gbase;
+    PaceState pace(it.pc);
     bf16x8 bhi[4], blo[4];
     bf16x8 ahi[4], alo[4];
     for (int64_t t = 0; t < nkt; ++t) {
@@ -656,17 +738,7 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
       for (int h = 0; h < 2; ++h) {
         // ---------------- L part
         if (h == 0) {
-          if (pace_left > 0 && ++since_pace == s.pace_kt) {
-            since_pace = 0;
-            --pace_left;
-            pace_t += pc.mult;
-            if (threadIdx.x == 0) xcd_pace(s.pace + 32 * xcd, pace_t);
-            if (pc.g && ++gcount == kChipPaceEvery) {  // ... and every other one chip-wide
-              gcount = 0;
-              gtarget += pc.gmult;
-              if (threadIdx.x == 0) xcd_pace(s.pace + 32 * 8, gtarget);
-            }
-          }
+          pace_point(s, it.pc, pace);
           if (since == s.flush_kt) {
             if constexpr (!idle) flush(slab, !flushed, acc, wave, lane);
             wait_vm<0>();
@@ -740,118 +812,46 @@ __device__ __forceinline__ void segment_h(const SSched& s, unsigned char* lds, i
     }
     if (!lag) bar();  // balance the stagger
   }
-  if (flushed && !idle) unflush(slab, acc, wave, lane);
-  if (partial) {
-#pragma unroll
-    for (int q = 0; q < NQUAD; ++q)
-      *slab_at(slab, wave, q, lane) = f32x4{acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    return;
-  }
-  if constexpr (idle) return;
-#pragma unroll
-  for (int q = 0; q < NQUAD; ++q) {
-    const float a[4] = {acc.at(q, 0), acc.at(q, 1), acc.at(q, 2), acc.at(q, 3)};
-    store4(s, i0 + 128 * wi + Acc::qrow(q, lane), j0 + 64 * wj + Acc::qcol(q, lane), diag, a);
-  }
+  finish_tile<idle>(s, tc, acc, flushed, it.partial);
 }
 
 __global__ __launch_bounds__(NTHR) void syrks_h_kernel(SSched s) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_B];
   const int L = xcd_logical(blockIdx.x, s.G);
   const int nwork = s.q + rem_rounds(s, L);
-  const int xcd = blockIdx.x & 7;
-  const unsigned nx = (unsigned)((s.G >> 3) + (xcd < (s.G & 7) ? 1 : 0));
-  // Full phases: every block runs P = NK / pace_kt points per tile.  Remainder rounds:
-  // Pm points per item, Pm from the shortest segment, so every item of a
-  // round runs the same count and the targets stay exact across rounds.
-  const unsigned P = s.pace_kt > 0 ? (unsigned)(s.NK / s.pace_kt) : 0u;
-  const int Pm = (s.pace_kt > 0 && s.nseg > 0) ? (int)(s.NK / s.nseg / s.pace_kt) : 0;
-  unsigned rbase = (unsigned)s.q * P * nx;
   for (int w = 0; w < nwork; ++w) {
-    int tile, slot = 0, sg = 0;
-    int64_t k0 = 0, k1 = s.NK;
-    const bool partial = w >= s.q;
-    PaceSeq pc{0, 0u, 0u};
-    if (!partial) {
-      tile = w * s.G + L;
-      pc = PaceSeq{(int)P, (unsigned)w * P * nx, nx};
-      pc.g = true;
-      pc.gbase = (unsigned)w * (P / kChipPaceEvery) * (unsigned)s.G;
-      pc.gmult = (unsigned)s.G;
-    } else {
-      rem_item(s, L, w - s.q, tile, slot, sg);
-      k0 = __builtin_amdgcn_readfirstlane((int)(s.NK * sg / s.nseg));
-      k1 = __builtin_amdgcn_readfirstlane((int)(s.NK * (sg + 1) / s.nseg));
-      if (Pm > 0) {
-        unsigned before = 0;
-        for (int u = 0; u < w - s.q; ++u) before += (unsigned)rem_active(s, L, u);
-        pc = PaceSeq{Pm, rbase + before * (unsigned)Pm, (unsigned)rem_active(s, L, w - s.q)};
-        // chip-wide: round u runs min(G, items - u G) items
-        const int items = s.R * s.nseg;
-        unsigned gb = (unsigned)s.q * (P / kChipPaceEvery) * (unsigned)s.G;
-        for (int u = 0; u < w - s.q; ++u)
-          gb += (unsigned)min(s.G, items - u * s.G) * (unsigned)(Pm / kChipPaceEvery);
-        pc.g = true;
-        pc.gbase = gb;
-        pc.gmult = (unsigned)min(s.G, items - (w - s.q) * s.G);
-      }
-    }
-    const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
+    const WorkItem it = work_item<true>(s, L, w);
+    const int tt = __builtin_amdgcn_readfirstlane(s.order[it.tile]);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool dg = (tt & 0xffff) == (tt >> 16);
     const int dw = 64 * (wv & 3) - 128 * (wv >> 2);
     if (dg && dw == 0)
-      segment_h<0>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<0>(s, lds, it);
     else if (dg && dw == 64)
-      segment_h<64>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<64>(s, lds, it);
     else if (dg && dw >= 128)  // waves 2 and 3: the whole block above the diagonal
-      segment_h<128>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<128>(s, lds, it);
     else if (dg)
-      segment_h<kDwDiag>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<kDwDiag>(s, lds, it);
     else
-      segment_h<kDwOff>(s, lds, tile, k0, k1, slot, partial, pc);
+      segment_h<kDwOff>(s, lds, it);
   }
 }
 
 // The fused-split kernel (d <= kFusedMaxD): persistent, one block per CU.
 __global__ __launch_bounds__(NTHR) void syrks_kernel(SSched s) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_B];
-  const int b = blockIdx.x;
-  const int L = xcd_logical(b, s.G);
-  // Full phases (w < q): every block walks all K of one tile, in lock-step with
-  // the rest.  Remainder: R tiles x nseg equal K segments, item i = seg * R + r,
-  // taken by logical block i mod G in round i / G.  Segment-major numbering
-  // keeps the items that run together (and, by the XCD-aware relabel, the ~G/8
-  // on one XCD) on the same K rows of neighbouring tiles, so their panels are
-  // shared in L2 rather than each item streaming its own K range from HBM.
-  const int items = s.R * s.nseg;
-  const int nwork = s.q + (L < items ? (items - 1 - L) / s.G + 1 : 0);
+  const int L = xcd_logical(blockIdx.x, s.G);
+  const int nwork = s.q + rem_rounds(s, L);
   for (int w = 0; w < nwork; ++w) {
-    int tile, slot = 0, cseg = 0;
-    int64_t k0 = 0, k1 = s.NK;
-    const bool partial = w >= s.q;
-    if (!partial) {
-      tile = w * s.G + L;
-    } else {
-      const int i = L + (w - s.q) * s.G;
-      const int sg = i / s.R, r = i - sg * s.R;
-      tile = s.q * s.G + r;
-      slot = i;
-      cseg = sg;
-      // (64-bit divisions run on the VALU: pin the bounds to SGPRs, the DMA
-      // descriptors built from them must be wave-uniform)
-      k0 = __builtin_amdgcn_readfirstlane((int)(s.NK * sg / s.nseg));
-      k1 = __builtin_amdgcn_readfirstlane((int)(s.NK * (sg + 1) / s.nseg));
-    }
-    // full phases pace (identical K work on every block); remainder items do not
-    const int pace_j = (!partial && s.pace_kt > 0) ? (int)(w * (s.NK / s.pace_kt)) : -1;
+    const WorkItem it = work_item<false>(s, L, w);
     // the lo^2 accumulation is compiled only into the copy that the diagonal tiles'
     // A-panel waves run
-    const int tt = __builtin_amdgcn_readfirstlane(s.order[tile]);
+    const int tt = __builtin_amdgcn_readfirstlane(s.order[it.tile]);
     if ((tt & 0xffff) == (tt >> 16) && (threadIdx.x >> 6) < 4)
-      segment<true>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
+      segment<true>(s, lds, it);
     else
-      segment<false>(s, lds, tile, k0, k1, slot, partial, pace_j, cseg);
+      segment<false>(s, lds, it);
   }
 }
 
@@ -1030,7 +1030,7 @@ struct Layout {
 };
 
 // Workspace: [order][G flush slabs][R * nseg remainder slabs][corr YB x dp][XP chunk].
-Layout make_layout(int64_t n, int64_t d, int G, int64_t chunk_rows) {
+Layout make_layout(int64_t d, int G, int64_t chunk_rows) {
   Layout L;
   L.dp = cdiv(d, BT) * BT;
   L.nt = L.dp / BT;
@@ -1055,7 +1055,6 @@ Layout make_layout(int64_t n, int64_t d, int G, int64_t chunk_rows) {
   L.off_xp = off;
   off += (size_t)chunk_rows * L.dp * 4;
   L.total = off;
-  (void)n;
   return L;
 }
 
@@ -1087,6 +1086,94 @@ int64_t default_chunk_rows(int64_t n, int64_t d) {
 // piece ~1.5 K-tiles of lead instead of one.
 constexpr int64_t kFusedMaxD = 2048;
 
+// K-tiles between two flushes of the accumulators, for a call of n rows.
+// Two-level fp32 summation: accumulators are added into a per-block slab every
+// flush_rows rows.  The error bound ~ (flush_rows / 32 + n / flush_rows) eps is
+// smallest at flush_rows ~ sqrt(32 n); each flush is a read-add-write of the block's
+// 256 KiB slab beside stalled MFMAs, and the measured error grows slowly above that
+// point, so the rule is 2^floor(log2 sqrt(128 n)) within [4096, 16384] (r05,
+// interleaved A/B with a float64 check of 64 sampled columns, tools/ab.py syrk,
+// profiles/r05z_syrk_flush_ab.log: config-3 shard 8192 -> 16384 rows 314.2 -> 308.6
+// ms, max error / max|S| 7.0e-7 -> 8.0e-7; config 2 4096 -> 8192 26.58 -> 25.78 ms,
+// 1.9e-7 -> 4.2e-7; 32768 rows at config 3: 305.8 ms but 1.4e-6, config 5's
+// n = 65536 at 16384: 2.0e-6 - not taken; r02: 4096 -> 8192 at config 3 337.6 ->
+// 331.1 ms, profiles/r02l_syrk_flush.log).
+int flush_ktiles(int64_t n) {
+#ifdef DEIG_AB_SYRK_FLUSH_ROWS
+  int64_t flush_rows = DEIG_AB_SYRK_FLUSH_ROWS;
+  (void)n;
+#else
+  int64_t flush_rows = 4096;
+  while (flush_rows < 16384 && (flush_rows * 2) * (flush_rows * 2) <= 128 * n) flush_rows *= 2;
+#endif
+  return flush_rows < ROWS_PAD ? 1 : (int)(flush_rows / ROWS_PAD);
+}
+
+// Everything of the schedule that one call fixes; a pass sets NK and beta (run_pass).
+SSched make_sched(const Layout& L, char* base, const float* X, int64_t n, int64_t d, int64_t ldx,
+                  float alpha, float* S, int64_t lds) {
+  SSched s;
+  s.XP = reinterpret_cast<unsigned char*>(base + L.off_xp);
+  s.S = S;
+  s.part = reinterpret_cast<float*>(base + L.off_part);
+  s.accs = reinterpret_cast<float*>(base + L.off_accs);
+  s.order = reinterpret_cast<const int*>(base + L.off_order);
+  s.lds = lds;
+  s.dp = L.dp;
+  s.NK = 0;
+  s.nseg = (int)L.nseg;
+  s.d = (int)d;
+  s.nt = (int)L.nt;
+  s.T = (int)L.T;
+  s.G = (int)L.G;
+  s.q = (int)L.q;
+  s.R = (int)L.R;
+  s.alpha = alpha;
+  s.beta = 0;
+  s.flush_kt = flush_ktiles(n);
+  s.pace = reinterpret_cast<unsigned*>(base + L.off_pace);
+  // XCD pacing every 64 K-tiles (2048 rows): config 3 L2 hit rate 0.52 -> 0.75, fabric
+  // read requests halved, 345 -> 334 ms (r02, interleaved A/B in one process;
+  // 16 / 32 / 128 / 256 K-tiles measured 0.3-1.5 % slower).
+  // Remainder rounds of the half ring are paced too (r04, interleaved A/B in one process,
+  // profiles/r04za_syrk_*_ab.log, unpaced / paced: config 2 - d = 3072, all 78 tiles
+  // remainder - 26.84 / 26.13 ms; d = 4096 22.78 / 22.45; d = 5120 71.8 / 66.7; config-3
+  // shard 303.5 / 305.0, within its ~1.5 ms spread): unpaced, the blocks of a remainder
+  // round drift apart over their ~2500 K-tiles as the full phases' did.  Numbering the
+  // remainder items XCD-major (each XCD's blocks on K ranges no other XCD reads) cost
+  // more in balance (nseg a multiple of 8) than it saved in L2 misses (27.15, 23.37,
+  // 72.6 ms at the same shapes).
+#ifdef DEIG_AB_SYRK_PACE
+  s.pace_kt = DEIG_AB_SYRK_PACE;
+#else
+  s.pace_kt = 64;
+#endif
+  s.X = X;
+  s.ldx = ldx;
+  s.nrows = n;
+  s.corr = reinterpret_cast<float*>(base + L.off_corr);
+  return s;
+}
+
+// One pass over s.NK K-tiles: the persistent kernel of this width, the sum of the
+// remainder slabs, then the diagonal's lo^2 term from the yb partial rows of s.corr.
+int run_pass(const SSched& s, const Layout& L, int64_t yb, hipStream_t stream) {
+  if (s.pace_kt > 0) DEIG_HIP_CHECK(hipMemsetAsync(s.pace, 0, 9 * 128, stream));
+  if (s.d <= kFusedMaxD)
+    hipLaunchKernelGGL(syrks_kernel, dim3((unsigned)L.G), dim3(NTHR), 0, stream, s);
+  else
+    hipLaunchKernelGGL(syrks_h_kernel, dim3((unsigned)L.G), dim3(NTHR), 0, stream, s);
+  DEIG_HIP_CHECK(hipGetLastError());
+  if (s.R > 0) {
+    hipLaunchKernelGGL(syrks_reduce_kernel, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
+    DEIG_HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(diag_corr_kernel, dim3((unsigned)cdiv(s.d, 64)), dim3(256), 0, stream, s.corr,
+                     (int)yb, L.dp, s.d, s.alpha, s.S, s.lds);
+  DEIG_HIP_CHECK(hipGetLastError());
+  return DEIG_OK;
+}
+
 }  // namespace
 
 // Persistent grid: one block per CU (measurement builds may set a smaller grid, for a
@@ -1101,8 +1188,7 @@ int syrk_cus() {
 
 size_t syrk_split_workspace_bytes(int64_t n, int64_t d) {
   if (n < 1 || d < 1) return 0;
-  if (d <= kFusedMaxD) return make_layout(n, d, syrk_cus(), 0).total;
-  return make_layout(n, d, syrk_cus(), default_chunk_rows(n, d)).total;
+  return make_layout(d, syrk_cus(), d <= kFusedMaxD ? 0 : default_chunk_rows(n, d)).total;
 }
 
 int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float alpha, float* S,
@@ -1117,68 +1203,16 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
   const int G = syrk_cus();
   const bool fused = d <= kFusedMaxD;
   // Largest chunk (multiple of 32 rows, <= n rounded up) that fits the workspace.
-  Layout L0 = make_layout(n, d, G, 0);
+  const Layout L0 = make_layout(d, G, 0);
   const size_t ws_min = L0.total + (fused ? 0 : (size_t)ROWS_PAD * L0.dp * 4);
   if (!ws || ws_bytes < ws_min)
     return fail(DEIG_EWORKSPACE, "syrk: workspace %zu bytes < minimum %zu", ws_bytes, ws_min);
   int64_t chunk = (int64_t)((ws_bytes - L0.total) / (size_t)(L0.dp * 4)) / ROWS_PAD * ROWS_PAD;
   const int64_t n32 = cdiv(n, ROWS_PAD) * ROWS_PAD;
   if (chunk > n32) chunk = n32;
-  const Layout L = make_layout(n, d, G, fused ? 0 : chunk);
+  const Layout L = make_layout(d, G, fused ? 0 : chunk);
   char* base = static_cast<char*>(ws);
-
-  SSched s;
-  s.S = S;
-  s.lds = lds;
-  s.dp = L.dp;
-  s.d = (int)d;
-  s.nt = (int)L.nt;
-  s.T = (int)L.T;
-  s.G = G;
-  s.q = (int)L.q;
-  s.R = (int)L.R;
-  s.alpha = alpha;
-  s.order = reinterpret_cast<const int*>(base + L.off_order);
-  s.accs = reinterpret_cast<float*>(base + L.off_accs);
-  s.part = reinterpret_cast<float*>(base + L.off_part);
-  s.XP = reinterpret_cast<const unsigned char*>(base + L.off_xp);
-  float* corr = reinterpret_cast<float*>(base + L.off_corr);
-  unsigned char* xp = reinterpret_cast<unsigned char*>(base + L.off_xp);
-
-  // Two-level fp32 summation: accumulators are added into a per-block slab every
-  // flush_rows rows.  The error bound ~ (flush_rows / 32 + n / flush_rows) eps is
-  // smallest at flush_rows ~ sqrt(32 n); each flush is a read-add-write of the block's
-  // 256 KiB slab beside stalled MFMAs, and the measured error grows slowly above that
-  // point, so the rule is 2^floor(log2 sqrt(128 n)) within [4096, 16384] (r05,
-  // interleaved A/B with a float64 check of 64 sampled columns, tools/ab.py syrk,
-  // profiles/r05z_syrk_flush_ab.log: config-3 shard 8192 -> 16384 rows 314.2 -> 308.6
-  // ms, max error / max|S| 7.0e-7 -> 8.0e-7; config 2 4096 -> 8192 26.58 -> 25.78 ms,
-  // 1.9e-7 -> 4.2e-7; 32768 rows at config 3: 305.8 ms but 1.4e-6, config 5's
-  // n = 65536 at 16384: 2.0e-6 - not taken; r02: 4096 -> 8192 at config 3 337.6 ->
-  // 331.1 ms, profiles/r02l_syrk_flush.log).
-#ifdef DEIG_AB_SYRK_FLUSH_ROWS
-  int64_t flush_rows = DEIG_AB_SYRK_FLUSH_ROWS;
-#else
-  int64_t flush_rows = 4096;
-  while (flush_rows < 16384 && (flush_rows * 2) * (flush_rows * 2) <= 128 * n) flush_rows *= 2;
-#endif
-  s.pace = reinterpret_cast<unsigned*>(base + L.off_pace);
-  // XCD pacing every 64 K-tiles (2048 rows): config 3 L2 hit rate 0.52 -> 0.75, fabric
-  // read requests halved, 345 -> 334 ms (r02, interleaved A/B in one process;
-  // 16 / 32 / 128 / 256 K-tiles measured 0.3-1.5 % slower).
-#ifdef DEIG_AB_SYRK_PACE
-  s.pace_kt = DEIG_AB_SYRK_PACE;
-#else
-  s.pace_kt = 64;
-#endif
-  // Remainder rounds are paced too (r04, interleaved A/B in one process,
-  // profiles/r04za_syrk_*_ab.log, unpaced / paced: config 2 - d = 3072, all 78 tiles
-  // remainder - 26.84 / 26.13 ms; d = 4096 22.78 / 22.45; d = 5120 71.8 / 66.7; config-3
-  // shard 303.5 / 305.0, within its ~1.5 ms spread): unpaced, the blocks of a remainder
-  // round drift apart over their ~2500 K-tiles as the full phases' did.  Numbering the
-  // remainder items XCD-major (each XCD's blocks on K ranges no other XCD reads) cost
-  // more in balance (nseg a multiple of 8) than it saved in L2 misses (27.15, 23.37,
-  // 72.6 ms at the same shapes).
+  SSched s = make_sched(L, base, X, n, d, ldx, alpha, S, lds);
   if (G == 256 && s.nt % 8 == 0)
     hipLaunchKernelGGL(tile_order_compact_kernel, dim3((unsigned)cdiv((s.nt / 8) * (s.nt / 8), 256)), dim3(256), 0,
                        stream, s.nt, reinterpret_cast<int*>(base + L.off_order));
@@ -1187,10 +1221,6 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
                        dim3((unsigned)cdiv(cdiv(s.nt, SUPER_H) * cdiv(s.nt, SUPER_W), 256)), dim3(256), 0, stream,
                        s.nt, reinterpret_cast<int*>(base + L.off_order));
   DEIG_HIP_CHECK(hipGetLastError());
-  s.X = X;
-  s.ldx = ldx;
-  s.nrows = n;
-  s.corr = corr;
   if (fused) {
     DEIG_REQUIRE(ldx <= (int64_t(1) << 25), "syrk: ldx > 2^25 is not supported for d <= 2048");
     // One pass over all n rows (no XP image, no chunks).  lo^2 partials:
@@ -1198,23 +1228,10 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
     const int64_t yb = 4 * (L.nseg > 1 ? L.nseg : 1);
     DEIG_REQUIRE(yb <= L.yb_max, "syrk: %lld lo^2 partial rows exceed the workspace's %lld",
                  (long long)yb, (long long)L.yb_max);
-    DEIG_HIP_CHECK(hipMemsetAsync(corr, 0, sizeof(float) * (size_t)(yb * L.dp), stream));
+    DEIG_HIP_CHECK(hipMemsetAsync(s.corr, 0, sizeof(float) * (size_t)(yb * L.dp), stream));
     s.NK = cdiv(n, ROWS_PAD);
-    s.nseg = (int)L.nseg;
     s.beta = accumulate ? 1 : 0;
-    s.flush_kt = (int)(flush_rows / ROWS_PAD);
-    if (s.flush_kt < 1) s.flush_kt = 1;
-    if (s.pace_kt > 0) DEIG_HIP_CHECK(hipMemsetAsync(s.pace, 0, 9 * 128, stream));
-    hipLaunchKernelGGL(syrks_kernel, dim3(G), dim3(NTHR), 0, stream, s);
-    DEIG_HIP_CHECK(hipGetLastError());
-    if (s.R > 0) {
-      hipLaunchKernelGGL(syrks_reduce_kernel, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
-      DEIG_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(diag_corr_kernel, dim3((unsigned)cdiv(d, 64)), dim3(256), 0, stream, corr,
-                       (int)yb, L.dp, (int)d, alpha, S, lds);
-    DEIG_HIP_CHECK(hipGetLastError());
-    return DEIG_OK;
+    return run_pass(s, L, yb, stream);
   }
   for (int64_t r0 = 0, c = 0; r0 < n; r0 += chunk, ++c) {
     const int64_t rows = (n - r0) < chunk ? (n - r0) : chunk;
@@ -1223,22 +1240,11 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
     int64_t yb = cdiv(noct, 4);
     if (yb > L.yb_max) yb = L.yb_max;
     hipLaunchKernelGGL(split_kernel, dim3((unsigned)(L.dp / 256), (unsigned)yb), dim3(256), 0,
-                       stream, X + r0 * ldx, rows, ldx, (int)d, L.dp, noct, xp, corr);
+                       stream, X + r0 * ldx, rows, ldx, (int)d, L.dp, noct, s.XP, s.corr);
     DEIG_HIP_CHECK(hipGetLastError());
     s.NK = nk;
-    s.nseg = (int)L.nseg;
     s.beta = (c > 0 || accumulate) ? 1 : 0;
-    s.flush_kt = (int)(flush_rows / ROWS_PAD);
-    if (s.pace_kt > 0) DEIG_HIP_CHECK(hipMemsetAsync(s.pace, 0, 9 * 128, stream));
-    hipLaunchKernelGGL(syrks_h_kernel, dim3(G), dim3(NTHR), 0, stream, s);
-    DEIG_HIP_CHECK(hipGetLastError());
-    if (s.R > 0) {
-      hipLaunchKernelGGL(syrks_reduce_kernel, dim3(s.R, SLAB / 4 / 256), dim3(256), 0, stream, s);
-      DEIG_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(diag_corr_kernel, dim3((unsigned)cdiv(d, 64)), dim3(256), 0, stream, corr,
-                       (int)yb, L.dp, (int)d, alpha, S, lds);
-    DEIG_HIP_CHECK(hipGetLastError());
+    if (int rc = run_pass(s, L, yb, stream)) return rc;
   }
   return DEIG_OK;
 }

@@ -23,11 +23,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def source_sha256():
     """Hash of the covariance kernel source the measurement describes (bench.py
     reports the traffic only while it still hashes the same).  syrk_split.hip holds
-    every kernel of the op (split, SYRK, reduce, diagonal correction); the shared
-    header only declares other modules' entry points, so it is not hashed."""
+    the kernels of the split3 op (split, SYRK, reduce, diagonal correction) and takes
+    its LDS-DMA and bf16 conversion primitives from lds_dma.hpp and bf16_split.hpp, so
+    all three are hashed, in this order.  The fp32 kernel (syrk.hip) is not part of the
+    measured op; deig_internal.hpp only declares other modules' entry points and small
+    host helpers, so it is not hashed."""
     h = hashlib.sha256()
-    h.update(open(os.path.join(ROOT, "distributed_eigenspaces_amd", "csrc", "syrk_split.hip"),
-                  "rb").read())
+    for name in ("syrk_split.hip", "lds_dma.hpp", "bf16_split.hpp"):
+        h.update(open(os.path.join(ROOT, "distributed_eigenspaces_amd", "csrc", name), "rb").read())
     return h.hexdigest()
 
 KERNELS = ["split_kernel", "syrks_kernel", "syrks_h_kernel", "syrks_reduce_kernel", "diag_corr_kernel",
