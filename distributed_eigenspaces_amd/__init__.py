@@ -14,6 +14,9 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
   * column_sums_u8 / sigma_hat_u8_centered / pca_transform_u8 - the same centred stack on
                      uint8 samples (exact integer covariance, bytes staged by the transform;
                      PCA(k, u8_mode="raw" | "gray"))
+  * sigma_hat_bf16 - bfloat16 samples as they are: one exact bf16 MFMA product, no float32
+                     copy (sigma_hat dispatches to it); column_sums, sigma_hat_centered,
+                     pca_transform, the estimator and PCA take bfloat16 without widening it
   * oja_step(s)    - mini-batch Oja (online variant, config 4); streaming.StreamingOja
                      adds the periodic all-gather / server solve / broadcast
 
@@ -23,7 +26,7 @@ compute_segma_hat, online loop).
 """
 from .linalg import (EigResult, column_sums, column_sums_u8, default_subspace,  # noqa: F401
                      oja_step, oja_steps, pca_transform, pca_transform_u8, procrustes_average,
-                     projavg_topk, projector_distance, sigma_hat, sigma_hat_centered,
+                     projavg_topk, projector_distance, sigma_hat, sigma_hat_bf16, sigma_hat_centered,
                      sigma_hat_u8_centered, stack_bases, subspace_distance, sym_apply, sym_power,
                      topk_eigh, topk_eigh_batch)
 from .pca import PCA  # noqa: F401

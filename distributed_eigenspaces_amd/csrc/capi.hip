@@ -148,6 +148,14 @@ int deig_syrk_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float alpha
   return deig_syrk_f32_ex(X, n, d, ldx, alpha, S, lds, DEIG_SYRK_DEFAULT, ws, ws_bytes, stream);
 }
 
+size_t deig_syrk_bf16_workspace(int64_t n, int64_t d) { return syrk_bf16_workspace_bytes(n, d); }
+
+int deig_syrk_bf16(const void* X, int64_t n, int64_t d, int64_t ldx, float alpha, float* S,
+                   int64_t lds, int flags, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return syrk_bf16_launch(X, n, d, ldx, alpha, S, lds, flags, ws, ws_bytes, (hipStream_t)stream);
+}
+
 size_t deig_syrk_shift_workspace(int64_t n, int64_t d, int xtype) {
   return syrk_shift_workspace_bytes(n, d, xtype);
 }
@@ -490,6 +498,18 @@ int deig_pca_transform_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, i
   g_err[0] = 0;
   return pca_transform_u8_launch(X, n, d, ldx, mode, mean, W, k, ldw, Y, ldy, resid, energy, ws,
                                  ws_bytes, (hipStream_t)stream);
+}
+
+size_t deig_pca_transform_bf16_workspace(int64_t n, int64_t d, int k) {
+  return pca_transform_bf16_workspace_bytes(n, d, k);
+}
+
+int deig_pca_transform_bf16(const void* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                            const float* W, int k, int64_t ldw, float* Y, int64_t ldy,
+                            float* resid, float* energy, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return pca_transform_bf16_launch(X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws,
+                                   ws_bytes, (hipStream_t)stream);
 }
 
 size_t deig_gemm_skinny_workspace(int64_t M, int64_t N, int64_t K) {

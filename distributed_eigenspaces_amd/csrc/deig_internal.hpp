@@ -33,6 +33,19 @@ const char* last_error();  // the calling thread's message (deig_last_error)
     if (!(cond)) return ::deig::fail(DEIG_EINVAL, __VA_ARGS__);                       \
   } while (0)
 
+// A DEIG_BF16 element: the upper 16 bits of the fp32 value; widening is exact.
+struct bf16_t {
+  uint16_t bits;
+  __host__ __device__ explicit operator float() const {
+    return __builtin_bit_cast(float, (uint32_t)bits << 16);
+  }
+  __host__ __device__ explicit operator double() const { return (double)(float)*this; }
+};
+
+// Bytes of an element of type xtype (DEIG_F32 / DEIG_F64 / DEIG_BF16): its alignment rule.
+inline size_t elem_bytes(int xtype) { return xtype == DEIG_F64 ? 8 : xtype == DEIG_BF16 ? 2 : 4; }
+inline bool known_elem(int xtype) { return xtype == DEIG_F32 || xtype == DEIG_F64 || xtype == DEIG_BF16; }
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -77,7 +90,13 @@ int syrk_split_launch(const float* X, int64_t n, int64_t d, int64_t ldx, float a
                       int64_t lds, void* ws, size_t ws_bytes, hipStream_t stream,
                       bool accumulate = false);
 
-// Mean-shifted covariance of float samples (shift.hip); xtype DEIG_F32 / DEIG_F64.
+// Covariance of bf16 samples as they are (syrk_bf16.hip): one exact MFMA product, two-level
+// fp32 summation; flags: 0 or DEIG_SYRK_ACCUMULATE.  Runs in row chunks sized by the workspace.
+size_t syrk_bf16_workspace_bytes(int64_t n, int64_t d);
+int syrk_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, float alpha, float* S,
+                     int64_t lds, int flags, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// Mean-shifted covariance of float samples (shift.hip); xtype DEIG_F32 / DEIG_F64 / DEIG_BF16.
 size_t syrk_shift_workspace_bytes(int64_t n, int64_t d, int xtype);
 int syrk_shift_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double alpha,
                       double* S64, int64_t lds64, float* S, int64_t lds, void* ws, size_t ws_bytes,
@@ -267,6 +286,13 @@ int pca_transform_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx,
                             const double* mean, const float* W, int k, int64_t ldw, float* Y,
                             int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
                             hipStream_t st);
+
+// The same from bf16 samples, widened (exactly) and centred when they are staged (pca_bf16.hip).
+size_t pca_transform_bf16_workspace_bytes(int64_t n, int64_t d, int k);
+int pca_transform_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                              const float* W, int k, int64_t ldw, float* Y, int64_t ldy,
+                              float* resid, float* energy, void* ws, size_t ws_bytes,
+                              hipStream_t st);
 
 // Procrustes-aligned basis average and residual-form subspace distance (procrustes.hip).
 // Both validate their arguments (DEIG_EINVAL) before any GPU work; the workspace

@@ -203,10 +203,10 @@ size_t syrk_shift_workspace_bytes(int64_t n, int64_t d, int xtype) {
 int syrk_shift_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double alpha,
                       double* S64, int64_t lds64, float* S, int64_t lds, void* ws, size_t ws_bytes,
                       hipStream_t st) {
-  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_F64, "syrk_shift: unknown element type %d", xtype);
+  DEIG_REQUIRE(known_elem(xtype), "syrk_shift: unknown element type %d", xtype);
   DEIG_REQUIRE(n >= 1 && d >= 1, "syrk_shift: need n >= 1, d >= 1");
   DEIG_REQUIRE(ldx >= d, "syrk_shift: ldx must be >= d");
-  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % (xtype == DEIG_F64 ? 8 : 4)) == 0,
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % elem_bytes(xtype)) == 0,
                "syrk_shift: X must be aligned to its element size");
   DEIG_REQUIRE(S64 || S, "syrk_shift: need S64 and/or S");
   DEIG_REQUIRE(!S64 || lds64 >= d, "syrk_shift: lds64 must be >= d");
@@ -217,6 +217,8 @@ int syrk_shift_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
   char* base = static_cast<char*>(ws);
   if (xtype == DEIG_F64)
     return shift_run(static_cast<const double*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st);
+  if (xtype == DEIG_BF16)
+    return shift_run(static_cast<const bf16_t*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st);
   return shift_run(static_cast<const float*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st);
 }
 
@@ -229,13 +231,13 @@ size_t syrk_centered_workspace_bytes(int64_t n, int64_t d, int xtype) {
 int syrk_centered_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
                          const double* center, double alpha, double* S64, int64_t lds64, float* S,
                          int64_t lds, double* mean_out, void* ws, size_t ws_bytes, hipStream_t st) {
-  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_F64, "syrk_centered: unknown element type %d", xtype);
+  DEIG_REQUIRE(known_elem(xtype), "syrk_centered: unknown element type %d", xtype);
   DEIG_REQUIRE(n >= 1 && d >= 1, "syrk_centered: need n >= 1, d >= 1");
   DEIG_REQUIRE(ldx >= d, "syrk_centered: ldx must be >= d");
   DEIG_REQUIRE(S64 || S, "syrk_centered: need S64 and/or S");
   DEIG_REQUIRE(!S64 || lds64 >= d, "syrk_centered: lds64 must be >= d");
   DEIG_REQUIRE(!S || lds >= d, "syrk_centered: lds must be >= d");
-  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % (xtype == DEIG_F64 ? 8 : 4)) == 0,
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % elem_bytes(xtype)) == 0,
                "syrk_centered: X must be aligned to its element size");
   DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % 8 == 0 &&
                    reinterpret_cast<uintptr_t>(mean_out) % 8 == 0,
@@ -246,6 +248,9 @@ int syrk_centered_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t
   char* base = static_cast<char*>(ws);
   if (xtype == DEIG_F64)
     return shift_run(static_cast<const double*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st,
+                     true, center, mean_out);
+  if (xtype == DEIG_BF16)
+    return shift_run(static_cast<const bf16_t*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st,
                      true, center, mean_out);
   return shift_run(static_cast<const float*>(X), n, d, ldx, alpha, S64, lds64, S, lds, base, L, st,
                    true, center, mean_out);
@@ -259,10 +264,10 @@ size_t colsum_workspace_bytes(int64_t n, int64_t d) {
 
 int colsum_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, double* sums,
                   void* ws, size_t ws_bytes, hipStream_t st) {
-  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_F64, "colsum: unknown element type %d", xtype);
+  DEIG_REQUIRE(known_elem(xtype), "colsum: unknown element type %d", xtype);
   DEIG_REQUIRE(n >= 1 && d >= 1, "colsum: need n >= 1, d >= 1");
   DEIG_REQUIRE(ldx >= d, "colsum: ldx must be >= d");
-  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % (xtype == DEIG_F64 ? 8 : 4)) == 0,
+  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) % elem_bytes(xtype)) == 0,
                "colsum: X must be aligned to its element size");
   DEIG_REQUIRE(sums && reinterpret_cast<uintptr_t>(sums) % 8 == 0, "colsum: sums must be 8-byte aligned");
   const size_t need = colsum_workspace_bytes(n, d);
@@ -273,6 +278,9 @@ int colsum_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, d
   const dim3 g((unsigned)cdiv(d, 256), (unsigned)yb);
   if (xtype == DEIG_F64)
     hipLaunchKernelGGL(colsum_kernel<double>, g, dim3(256), 0, st, static_cast<const double*>(X), n,
+                       ldx, d, part);
+  else if (xtype == DEIG_BF16)
+    hipLaunchKernelGGL(colsum_kernel<bf16_t>, g, dim3(256), 0, st, static_cast<const bf16_t*>(X), n,
                        ldx, d, part);
   else
     hipLaunchKernelGGL(colsum_kernel<float>, g, dim3(256), 0, st, static_cast<const float*>(X), n,

@@ -1,0 +1,347 @@
+// Covariance of bf16 samples taken as they are (deig_syrk_bf16):  S = alpha X^T X (+ S).
+// A bf16 x bf16 product is exact in fp32 (8 x 8 significant bits), so one
+// v_mfma_f32_16x16x32_bf16 product per fragment pair gives what the split3 kernel
+// (syrk_split.hip) needs three for on a widened copy - whose lo pieces are all zero - and
+// there is no split pass, no fp32 copy and no lo*lo diagonal correction.  The only error is
+// the fp32 summation, kept two-level: no MFMA accumulator takes more than kFlushRows = 16384
+// rows before it is written out as a partial, and the partials are added in a fixed order.
+//
+// Pipeline, per row chunk (the chunk is what the workspace's image holds):
+//  * bf16_prep_kernel relays the chunk of X into an image in MFMA operand order:
+//    [k-step of 32 rows][g = 8-row group][feature, padded to 128][8 rows = 16 B], the 16
+//    bytes lane (g, feature) feeds to the MFMA.  Rows past n and features past d are zero;
+//    no element behind column d of a row is read.
+//  * bf16_syrk_kernel: one workgroup per (lower 128 x 128 tile, K segment), 4 waves with
+//    64 x 64 wave tiles (4 x 4 MFMA blocks), LDS double buffer of 64-row stages (two MFMA
+//    K-steps per barrier) fed from a register ring of 16-byte loads, ds_read_b128 operand
+//    reads, fp32 accumulators.  Each item stores its accumulators to a slab of its own
+//    (fragment order: one 16-byte store per lane and MFMA block, fully coalesced).  Plain
+//    independent workgroups: nobody waits on anybody, no atomics.
+//  * bf16_reduce_kernel: one workgroup per tile adds the segments' slabs in order, applies
+//    alpha, adds S when accumulating (the caller's flag, and every chunk after the first),
+//    and writes S[i][j] and, through LDS, the mirror S[j][i] from the same value.
+// Every slab entry that is read was written by this call (a diagonal tile's upper wave
+// block is neither), so the workspace may hold anything on entry.
+#include "bf16_split.hpp"
+
+namespace deig {
+namespace {
+
+constexpr int KB = 32;              // rows per MFMA K-step
+// Tuning constants; a measurement build overrides them (_build.build_library(defines=...)).
+// 32-row stages with a 4-deep ring fit 3 workgroups per CU (166 VGPRs, 32 KiB LDS): 7 %
+// faster at 2^20 x 3072, 2.6 % slower at 2^19 x 8192 than the values below (DESIGN Appendix A).
+#ifndef DEIG_AB_BF16_STAGE_ROWS
+#define DEIG_AB_BF16_STAGE_ROWS 64
+#endif
+#ifndef DEIG_AB_BF16_PF
+#define DEIG_AB_BF16_PF 2
+#endif
+#ifndef DEIG_AB_BF16_WGS
+#define DEIG_AB_BF16_WGS 2
+#endif
+constexpr int SB = DEIG_AB_BF16_STAGE_ROWS;  // rows per LDS stage (a multiple of KB)
+constexpr int KS = SB / 32;                  // K-steps per stage
+constexpr int NH = 2 * KS;                   // 16-byte pieces per thread, panel and stage
+constexpr int PF = DEIG_AB_BF16_PF;          // stages in the register ring (even)
+constexpr int WGS = DEIG_AB_BF16_WGS;        // workgroups per CU the kernel is built for
+constexpr int TB = 128;             // output tile edge (features)
+constexpr int THR = 256;            // 4 waves, 2 x 2 wave tiles of 64 x 64
+constexpr int kFlushRows = 16384;   // rows per K segment at most (syrk_split.hip flush_ktiles)
+constexpr int kSegStages = kFlushRows / SB;
+constexpr int kMinSegs = 4, kMaxSegs = 32;
+constexpr int kItemsTarget = 512;   // two workgroups on each of 256 CUs
+constexpr int64_t kTileFloats = (int64_t)TB * TB;
+
+// Image: [kb][g][feature][8 rows]; stage st is the K-steps kb = KS st .. KS st + KS - 1.
+__host__ __device__ inline int64_t img_off(int64_t kb, int g, int64_t f, int64_t fpad) {
+  return ((kb * 4 + g) * fpad + f) * 16;
+}
+
+// grid (cdiv(fpad, 512), YB): wave g of a block owns the 8-row group g of K-steps kb =
+// by, by + YB, ..., lane l the features 512 bx + 8 l .. + 7: eight 16-byte row loads (1 KiB
+// contiguous per row and wave), an 8 x 8 transpose of 16-bit values in registers, eight
+// 16-byte stores (128 contiguous bytes per lane, 8 KiB per wave).
+__global__ __launch_bounds__(THR) void bf16_prep_kernel(const uint16_t* __restrict__ X, int64_t n,
+                                                        int64_t ldx, int64_t d, int64_t fpad,
+                                                        int64_t nkb, uint8_t* __restrict__ img) {
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int64_t f = (int64_t)blockIdx.x * 512 + lane * 8;
+  if (f >= fpad) return;
+  const bool fin = f < d;  // d % 8 == 0: the 8 features are all in or all out
+  for (int64_t kb = blockIdx.y; kb < nkb; kb += gridDim.y) {
+    u32x4 rows[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int64_t row = kb * KB + g * 8 + r;
+      rows[r] = (fin && row < n) ? *reinterpret_cast<const u32x4*>(X + row * ldx + f)
+                                 : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {  // features 2 w (low halves) and 2 w + 1 (high halves)
+      u32x4 lo, hi;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {  // rows 2 q, 2 q + 1
+        const uint32_t a = rows[2 * q][w], b = rows[2 * q + 1][w];
+        lo[q] = (a & 0xffffu) | (b << 16);
+        hi[q] = (a >> 16) | (b & 0xffff0000u);
+      }
+      *reinterpret_cast<u32x4*>(img + img_off(kb, g, f + 2 * w, fpad)) = lo;
+      *reinterpret_cast<u32x4*>(img + img_off(kb, g, f + 2 * w + 1, fpad)) = hi;
+    }
+  }
+}
+
+// Lower tile t (row-major over the triangle) -> (ti, tj), tj <= ti.
+__device__ __forceinline__ void tile_of(int t, int& ti, int& tj) {
+  int i = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+  while (i * (i + 1) / 2 > t) --i;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  ti = i;
+  tj = t - i * (i + 1) / 2;
+}
+
+struct Bf16Sched {
+  const uint8_t* img;
+  float* slabs;  // [seg][tile][wave][MFMA block a, b][lane][4]
+  int64_t nst, fpad;  // SB-row stages of the chunk
+  int T, nseg;
+};
+
+// One item = (lower tile, K segment).  LDS: 2 stages x (A panel, B panel), a panel = 4 KS row
+// groups x 128 features x 16 B (16 KiB at SB = 64), the same bytes as the image's runs.  Wave (wi, wj)
+// owns rows 64 wi.. and columns 64 wj.. of the tile; lane l reads the fragment of feature
+// 16 a + (l & 15), row group l >> 4 of a K-step: within a ds_read_b128 lane group the 16
+// addresses cover 64 distinct banks.
+__global__ __launch_bounds__(THR, WGS) void bf16_syrk_kernel(Bf16Sched s) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[2][2][KS * 4 * TB * 16];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
+  const int item = blockIdx.x;
+  const int tile = item % s.T, seg = item / s.T;
+  int ti, tj;
+  tile_of(tile, ti, tj);
+  const bool diag = ti == tj;
+  const bool active = !(diag && wi < wj);  // the upper block of a diagonal tile is a mirror
+  const int64_t k0 = s.nst * seg / s.nseg, k1 = s.nst * (seg + 1) / s.nseg;
+  const int64_t i0 = (int64_t)ti * TB, j0 = (int64_t)tj * TB;
+  if (k0 >= k1) return;  // (never: nseg <= nst; whole block)
+
+  // staging: thread t moves the 16-byte pieces c = t + 256 h of each panel (4 KS row groups
+  // x 128 features)
+  auto load = [&](int64_t st, u32x4 (&ra)[NH], u32x4 (&rb)[NH]) {
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int c = tid + h * THR;
+      const int grp = c >> 7, fl = c & 127;
+      // (unconditional: a diagonal tile loads its panel twice - a branch around the B loads
+      // would make the compiler's counted waits conservative)
+      ra[h] = *reinterpret_cast<const u32x4*>(s.img + img_off(KS * st + (grp >> 2), grp & 3, i0 + fl, s.fpad));
+      rb[h] = *reinterpret_cast<const u32x4*>(s.img + img_off(KS * st + (grp >> 2), grp & 3, j0 + fl, s.fpad));
+    }
+  };
+  auto put = [&](int b, const u32x4 (&ra)[NH], const u32x4 (&rb)[NH]) {
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int c = tid + h * THR;
+      *reinterpret_cast<u32x4*>(&lds[b][0][c * 16]) = ra[h];
+      *reinterpret_cast<u32x4*>(&lds[b][1][c * 16]) = rb[h];
+    }
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // K loop: LDS double buffer fed from a PF-deep register ring - the loads of stage kk + PF
+  // are issued while kk's MFMAs run.  Loads are unpredicated (clamped to the last stage) so
+  // that the compiler's counted waits keep the ring in flight; PF even: buffer = u & 1.
+  u32x4 ra[PF][NH], rb[PF][NH];
+  auto clampk = [&](int64_t st) { return st < k1 ? st : k1 - 1; };
+#pragma unroll
+  for (int u = 0; u < PF; ++u) load(clampk(k0 + u), ra[u], rb[u]);
+  put(0, ra[0], rb[0]);
+  __syncthreads();
+  const int g = lane >> 4, c = lane & 15;
+  auto body = [&](int64_t kk, int u) {
+    load(clampk(kk + PF), ra[u], rb[u]);  // slot u's stage is already in LDS
+    const int b = u & 1;
+    if (active) {
+      const uint8_t* pa = &lds[b][0][0];
+      const uint8_t* pb = diag ? pa : &lds[b][1][0];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        bf16x8 fa[4], fb[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+          fa[a] = *reinterpret_cast<const bf16x8*>(pa + ((ks * 4 + g) * TB + 64 * wi + 16 * a + c) * 16);
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb)
+          fb[bb] = *reinterpret_cast<const bf16x8*>(pb + ((ks * 4 + g) * TB + 64 * wj + 16 * bb + c) * 16);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb)
+            acc[a][bb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[bb], acc[a][bb], 0, 0, 0);
+      }
+    }
+    put(b ^ 1, ra[(u + 1) % PF], rb[(u + 1) % PF]);  // stage kk + 1 (a clamped copy past k1)
+    __syncthreads();
+  };
+  int64_t kk = k0;
+  for (; kk + PF <= k1; kk += PF) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) body(kk + u, u);
+  }
+#pragma unroll
+  for (int u = 0; u < PF; ++u)
+    if (kk + u < k1) body(kk + u, u);
+  if (!active) return;
+  // the slab of this item, in fragment order: block (a, b) of the wave is 64 lanes x 16 B
+  f32x4* slab = reinterpret_cast<f32x4*>(s.slabs + ((int64_t)seg * s.T + tile) * kTileFloats) +
+                wave * 16 * 64 + lane;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) slab[(a * 4 + b) * 64] = acc[a][b];
+}
+
+// One workgroup per lower tile, one 64-row half of it at a time.  C/D map of the MFMA:
+// lane l, register r of block (a, b) of wave (wi, wj) is row 64 wi + 16 a + 4 (l >> 4) + r,
+// column 64 wj + 16 b + (l & 15) of the tile.  v = alpha (sum of the segments in order)
+// (+ S[i][j], the lower entry, when accumulating) goes to LDS (row stride 129: both the row
+// and the column walk are conflict-free), then to S[i][j] in rows of 128 contiguous floats
+// and to S[j][i] in runs of 64: both triangles hold the same bits.
+__global__ __launch_bounds__(THR) void bf16_reduce_kernel(const float* __restrict__ slabs, int T,
+                                                          int nseg, float alpha, int beta,
+                                                          float* __restrict__ S, int64_t lds,
+                                                          int64_t d) {
+  __shared__ float V[64][TB + 1];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x;
+  int ti, tj;
+  tile_of(tile, ti, tj);
+  const bool diag = ti == tj;
+  const int64_t j0 = (int64_t)tj * TB;
+  for (int h = 0; h < 2; ++h) {
+    const int64_t i0 = (int64_t)ti * TB + 64 * h;
+    for (int q = tid; q < 2048; q += THR) {
+      const int wj = q >> 10, ab = (q >> 6) & 15, lane = q & 63;
+      if (diag && h < wj) continue;  // not computed, and only mirrors
+      const int64_t e = ((int64_t)((2 * h + wj) * 16 + ab) * 64 + lane) * 4;
+      const float* p = slabs + (int64_t)tile * kTileFloats + e;
+      f32x4 v = *reinterpret_cast<const f32x4*>(p);
+      for (int sg = 1; sg < nseg; ++sg)
+        v += *reinterpret_cast<const f32x4*>(p + (int64_t)sg * T * kTileFloats);
+      const int jl = 64 * wj + 16 * (ab & 3) + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int il = 16 * (ab >> 2) + 4 * (lane >> 4) + r;
+        const int64_t i = i0 + il, j = j0 + jl;
+        float x = alpha * v[r];
+        if (beta && i < d && j < d && j <= i) x += S[i * lds + j];
+        V[il][jl] = x;
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 64 * TB; idx += THR) {
+      const int il = idx >> 7, jl = idx & 127;
+      const int64_t i = i0 + il, j = j0 + jl;
+      if (i < d && j < d && j <= i) S[i * lds + j] = V[il][jl];
+    }
+    for (int idx = tid; idx < 64 * TB; idx += THR) {
+      const int jl = idx >> 6, il = idx & 63;
+      const int64_t i = i0 + il, j = j0 + jl;
+      if (i < d && j < d && j < i) S[j * lds + i] = V[il][jl];
+    }
+    __syncthreads();
+  }
+}
+
+struct Bf16Layout {
+  int64_t fpad, T, max_rows;
+  int max_segs;
+  size_t off_img, row_bytes;
+};
+
+// The slabs are sized by d alone (max_segs segments of every lower tile), so what a given
+// workspace leaves for the image, and with it the chunk, does not depend on n.
+Bf16Layout bf16_layout(int64_t d) {
+  Bf16Layout L;
+  L.fpad = cdiv(d, TB) * TB;
+  const int64_t nt = L.fpad / TB;
+  L.T = nt * (nt + 1) / 2;
+  int64_t segs = cdiv(kItemsTarget, L.T);
+  L.max_segs = (int)(segs < kMinSegs ? kMinSegs : segs > kMaxSegs ? kMaxSegs : segs);
+  L.max_rows = (int64_t)L.max_segs * kFlushRows;
+  L.off_img = align_up(sizeof(float) * (size_t)L.max_segs * L.T * kTileFloats, 256);
+  L.row_bytes = (size_t)L.fpad * 2;
+  return L;
+}
+
+int64_t pad_rows(int64_t n) { return cdiv(n, SB) * SB; }
+
+}  // namespace
+
+size_t syrk_bf16_workspace_bytes(int64_t n, int64_t d) {
+  if (n < 1 || d < 1 || d > (1 << 15)) return 0;
+  const Bf16Layout L = bf16_layout(d);
+  const int64_t rows = pad_rows(n) < L.max_rows ? pad_rows(n) : L.max_rows;
+  return L.off_img + (size_t)rows * L.row_bytes;
+}
+
+int syrk_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, float alpha, float* S,
+                     int64_t lds, int flags, void* ws, size_t ws_bytes, hipStream_t stream) {
+  DEIG_REQUIRE((flags & ~DEIG_SYRK_ACCUMULATE) == 0, "syrk_bf16: unknown flag bits 0x%x", flags);
+  DEIG_REQUIRE(n >= 1, "syrk_bf16: n must be >= 1 (got %lld)", (long long)n);
+  DEIG_REQUIRE(d >= 8 && d % 8 == 0 && d <= (1 << 15),
+               "syrk_bf16: d must be a multiple of 8 in [8, 32768] (got %lld)", (long long)d);
+  DEIG_REQUIRE(ldx >= d, "syrk_bf16: ldx must be >= d");
+  DEIG_REQUIRE(ldx % 8 == 0, "syrk_bf16: ldx must be a multiple of 8 elements");
+  DEIG_REQUIRE(X && S, "syrk_bf16: X and S must not be NULL");
+  DEIG_REQUIRE(aligned16(X) && aligned16(S), "syrk_bf16: X and S must be 16-byte aligned");
+  DEIG_REQUIRE(lds >= d && lds % 4 == 0, "syrk_bf16: lds must be >= d and a multiple of 4");
+  const Bf16Layout L = bf16_layout(d);
+  const size_t least = L.off_img + (size_t)SB * L.row_bytes;
+  if (!ws || ws_bytes < least)
+    return fail(DEIG_EWORKSPACE, "syrk_bf16: workspace %zu bytes < required %zu", ws_bytes, least);
+  int64_t chunk = (int64_t)((ws_bytes - L.off_img) / (L.row_bytes * SB)) * SB;
+  if (chunk > L.max_rows) chunk = L.max_rows;
+  char* base = static_cast<char*>(ws);
+  Bf16Sched s;
+  s.img = reinterpret_cast<const uint8_t*>(base + L.off_img);
+  s.slabs = reinterpret_cast<float*>(base);
+  s.fpad = L.fpad;
+  s.T = (int)L.T;
+  const uint16_t* Xe = static_cast<const uint16_t*>(X);
+  int beta = (flags & DEIG_SYRK_ACCUMULATE) ? 1 : 0;
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
+    const int64_t nst = cdiv(rows, SB), nkb = KS * nst;
+    // K segments: enough items for two workgroups per CU, each at most kFlushRows rows
+    // (the two-level summation) and at least 4 stages (the staging prologue)
+    int64_t nseg = cdiv(kItemsTarget, L.T);
+    if (nseg > L.max_segs) nseg = L.max_segs;
+    if (nseg > nst / 4) nseg = nst / 4;
+    if (nseg < cdiv(nst, kSegStages)) nseg = cdiv(nst, kSegStages);
+    if (nseg < 1) nseg = 1;
+    s.nst = nst;
+    s.nseg = (int)nseg;  // <= max_segs: nst <= max_segs * kSegStages
+    const int yb = (int)(nkb < 256 ? nkb : 256);
+    hipLaunchKernelGGL(bf16_prep_kernel, dim3((unsigned)cdiv(L.fpad, 512), (unsigned)yb), dim3(THR),
+                       0, stream, Xe + r0 * ldx, rows, ldx, d, L.fpad, nkb,
+                       reinterpret_cast<uint8_t*>(base + L.off_img));
+    DEIG_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bf16_syrk_kernel, dim3((unsigned)(L.T * nseg)), dim3(THR), 0, stream, s);
+    DEIG_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bf16_reduce_kernel, dim3((unsigned)L.T), dim3(THR), 0, stream, s.slabs, s.T,
+                       s.nseg, alpha, beta, S, lds, d);
+    DEIG_HIP_CHECK(hipGetLastError());
+    beta = 1;
+  }
+  return DEIG_OK;
+}
+
+}  // namespace deig

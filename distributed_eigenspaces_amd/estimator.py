@@ -28,6 +28,11 @@ one byte each) or v = (r + g + b) / 3 of interleaved pixels ("gray": (n, H, W, 3
 3-byte pixels), and ``EstimatorResult.mean`` is in units of v.  Without ``u8_mode`` uint8
 samples are widened to float64 as before.
 
+bfloat16 samples (a tensor on the device) stay bfloat16 with either setting of ``center``:
+the workers' covariance is ``linalg.sigma_hat``'s bf16 kernel (one exact MFMA product, no
+float32 copy) or, centred, ``linalg.sigma_hat_centered`` reading bf16, and the column sums of
+the pooled mean read bf16 too.
+
 The collective layer only uses ``torch.distributed`` with tensors on the rank's
 device, so it runs on ``gloo`` with CPU tensors too (multi-process tests); the
 per-worker compute is injectable for those tests and defaults to the GPU ops.

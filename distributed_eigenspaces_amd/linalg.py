@@ -27,6 +27,7 @@ __all__ = [
     "procrustes_average", "subspace_distance", "projector_distance", "ProcrustesResult",
     "column_sums", "sigma_hat_centered", "pca_transform",
     "column_sums_u8", "sigma_hat_u8_centered", "pca_transform_u8",
+    "sigma_hat_bf16", "bf16_device_tensor",
 ]
 
 DEFAULT_TOL = 1e-6
@@ -107,6 +108,32 @@ def require_device_tensor(t, name: str = "input", keep_f64: bool = False) -> tor
     return t
 
 
+def bf16_device_tensor(t: torch.Tensor, name: str = "input") -> torch.Tensor:
+    """A bfloat16 tensor on a ROCm device, kept bfloat16 (host tensors are copied over)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
+    if t.dtype != torch.bfloat16:
+        raise ValueError(f"{name} needs bfloat16 samples, got {t.dtype}")
+    if t.device.type != "cuda":
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    return t
+
+
+def _rowmajor_8_bf16(t: torch.Tensor, name: str) -> torch.Tensor:
+    """``_rowmajor_4`` for bfloat16 samples: a 2-D row-major view with unit column stride,
+    columns and row stride % 8 == 0, 16-B aligned; anything else is copied into a zero-padded
+    BFLOAT16 tensor (never a float32 one), so what lies behind the columns never enters."""
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be 2-D, got shape {tuple(t.shape)}")
+    ok = (t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1]
+          and t.shape[1] % 8 == 0 and t.data_ptr() % 16 == 0)
+    if ok:
+        return t
+    out = torch.zeros((t.shape[0], (t.shape[1] + 7) // 8 * 8), dtype=torch.bfloat16, device=t.device)
+    out[:, :t.shape[1]] = t
+    return out
+
+
 def _rowmajor_4(t: torch.Tensor, name: str) -> torch.Tensor:
     """2-D row-major view with unit column stride, columns and row stride % 4 == 0, 16-B
     aligned; anything else (a 37-column slice of a 40-column tensor included) is copied
@@ -153,7 +180,9 @@ def _check_k(k, d: int) -> int:
 
 
 def _elem_type(dtype: torch.dtype) -> int:
-    """The library's element-type code of a float32 / float64 operand."""
+    """The library's element-type code of a float32 / float64 / bfloat16 operand."""
+    if dtype == torch.bfloat16:
+        return _lib.DEIG_BF16
     return _lib.DEIG_F64 if dtype == torch.float64 else _lib.DEIG_F32
 
 
@@ -204,7 +233,10 @@ def sigma_hat(x: torch.Tensor, alpha: float | None = None,
         terms are added in double) returned as float64 - the small eigenvectors of an
         uncentered covariance keep float64 parity (csrc/shift.hip);
       * uint8 samples: the exact integer path (sigma_hat_u8; 2-D raw bytes or
-        N x H x W x 3 pixels with the reference's grayscale fused in).
+        N x H x W x 3 pixels with the reference's grayscale fused in);
+      * bfloat16 samples: taken as they are (sigma_hat_bf16: one exact bf16 MFMA product,
+        no float32 copy; ``accumulate`` works as for float32); with ``shift=True`` the
+        mean-shifted path reads them as bf16 too.
     dtype: result dtype (float32 / float64) for the shifted and uint8 paths.
     accumulate: ``out += alpha X^T X`` (float32 split3 path; a covariance streamed
     through in row blocks, DEIG_SYRK_ACCUMULATE).
@@ -213,6 +245,8 @@ def sigma_hat(x: torch.Tensor, alpha: float | None = None,
         x = torch.as_tensor(x)
     if x.dtype == torch.uint8:
         return sigma_hat_u8(x, alpha=alpha, out=out, dtype=dtype or torch.float32)
+    if x.dtype == torch.bfloat16 and not shift:
+        return sigma_hat_bf16(x, alpha=alpha, out=out, accumulate=accumulate)
     if shift is None:
         shift = x.dtype == torch.float64
     if shift:
@@ -251,6 +285,46 @@ def sigma_hat(x: torch.Tensor, alpha: float | None = None,
     return S
 
 
+def sigma_hat_bf16(x: torch.Tensor, alpha: float | None = None,
+                   out: torch.Tensor | None = None, accumulate: bool = False) -> torch.Tensor:
+    """Sigma_hat = alpha * X^T X (alpha = 1/n by default) of bfloat16 samples, read as they
+    are (include/deig.h deig_syrk_bf16): every bf16 x bf16 product is exact in float32, so
+    one MFMA product per fragment pair and a two-level float32 summation - no float32 copy
+    of x, no hi/lo split.  Returns a (d, d) float32 tensor, bit-exactly symmetric.
+    x: (n, d) bfloat16 on the GPU (host tensors are copied over); a view that is not
+    row-major with d % 8 == 0, a row stride % 8 == 0 and 16-byte alignment is copied into a
+    zero-padded bfloat16 tensor.  accumulate: ``out += alpha X^T X`` (out: contiguous
+    (d, d) float32, d % 8 == 0), a covariance streamed through in row blocks."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(x)
+    x = bf16_device_tensor(x, "sigma_hat_bf16")
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2-D (n, d), got {tuple(x.shape)}")
+    n, d = x.shape
+    direct = (out is not None and d % 8 == 0 and out.shape == (d, d) and out.is_contiguous()
+              and out.dtype == torch.float32 and out.device == x.device)
+    if accumulate and not direct:
+        raise ValueError("accumulate needs out (contiguous d x d float32 on x's device) and "
+                         "d % 8 == 0")
+    if n == 0:
+        return _nan_cov(d, torch.float32, x.device)
+    xx = _rowmajor_8_bf16(x, "x")
+    dp = xx.shape[1]
+    S = out if direct else torch.empty((dp, dp), dtype=torch.float32, device=x.device)
+    _call(x.device, "deig_syrk_bf16",
+          (xx.data_ptr(), n, dp, _ld(xx, 0, dp), _alpha(alpha, n), S.data_ptr(), S.stride(0),
+           _lib.DEIG_SYRK_ACCUMULATE if accumulate else 0),
+          "deig_syrk_bf16_workspace", (n, dp))
+    if direct:
+        return out
+    if dp != d:
+        S = S[:d, :d].contiguous()
+    if out is not None:
+        out.copy_(S)
+        return out
+    return S
+
+
 def sigma_hat_shift(x: torch.Tensor, alpha: float | None = None,
                     out: torch.Tensor | None = None,
                     dtype: torch.dtype = torch.float64) -> torch.Tensor:
@@ -277,12 +351,16 @@ def sigma_hat_shift(x: torch.Tensor, alpha: float | None = None,
 
 
 def _float_samples(x, name: str) -> torch.Tensor:
-    """(n, d) float32 / float64 samples on the device with unit column stride."""
+    """(n, d) float32 / float64 / bfloat16 samples on the device with unit column stride
+    (bfloat16 stays bfloat16: DEIG_BF16)."""
     if not isinstance(x, torch.Tensor):
         x = torch.as_tensor(x)
-    if x.dtype not in (torch.float32, torch.float64):
-        x = x.to(torch.float64)
-    x = require_device_tensor(x, name, keep_f64=True)
+    if x.dtype == torch.bfloat16:
+        x = bf16_device_tensor(x, name)
+    else:
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        x = require_device_tensor(x, name, keep_f64=True)
     if x.dim() != 2:
         raise ValueError(f"x must be 2-D (n, d), got {tuple(x.shape)}")
     if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
@@ -1007,10 +1085,13 @@ def pca_transform(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = 
 
     X (n, d) row-major, W (d, k) any layout with k <= 256, mean (d,) or None (no
     centring).  The mean is subtracted in double before the product.  float64 X is centred
-    in float64 here and then rounded to float32 (the kernel reads float32).  Returns Y, or
+    in float64 here and then rounded to float32 (the kernel reads float32); bfloat16 X is
+    read as it is (deig_pca_transform_bf16: widened and centred when staged).  Returns Y, or
     the tuple (Y[, residual][, energy])."""
     if not isinstance(X, torch.Tensor):
         X = torch.as_tensor(X)
+    if X.dtype == torch.bfloat16:
+        return _pca_transform_bf16(X, W, mean, residual, energy)
     mu = None
     if mean is not None:
         mu = torch.as_tensor(mean).to(dtype=torch.float64).reshape(-1)
@@ -1027,6 +1108,27 @@ def pca_transform(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = 
               (X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp),
                Y.data_ptr(), _ld(Y, 0, k), _ptr(res), _ptr(en)),
               "deig_pca_transform_workspace", (n, dp, k))
+    return _transform_result(Y, res, en)
+
+
+def _pca_transform_bf16(X, W, mean, residual: bool, energy: bool):
+    """``pca_transform`` of bfloat16 samples (include/deig.h deig_pca_transform_bf16)."""
+    X = _rowmajor_8_bf16(bf16_device_tensor(X, "pca_transform"), "X")
+    n, dp = X.shape
+    dev = X.device
+    W = require_device_tensor(W, "W")
+    if W.dim() != 2:
+        raise ValueError(f"W must be 2-D (d, k), got shape {tuple(W.shape)}")
+    d = W.shape[0]
+    if d > dp or (dp != d and dp != (d + 7) // 8 * 8):
+        raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
+    W, mu, k = _transform_operands(W, d, dp, mean, dev, "W")
+    Y, res, en = _transform_buffers(n, k, dev, residual, energy)
+    if n > 0:
+        _call(dev, "deig_pca_transform_bf16",
+              (X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp),
+               Y.data_ptr(), _ld(Y, 0, k), _ptr(res), _ptr(en)),
+              "deig_pca_transform_bf16_workspace", (n, dp, k))
     return _transform_result(Y, res, en)
 
 

@@ -14,7 +14,9 @@ is the opt-in centred counterpart:
   descending variance, and gives ``explained_variance_``.
 * ``transform`` / ``reconstruction_error``: the fused centred transform kernel.
 
-Float32 and float64 samples by default.  uint8 samples are opt-in through
+Float32, float64 and bfloat16 samples by default (bfloat16 is read as it is by the column
+sums, the centred covariance and the transform's bf16 kernel; ``mean_`` stays float64 and
+``components_`` float32).  uint8 samples are opt-in through
 ``PCA(k, u8_mode="raw")`` (features v = x, one byte each) or ``u8_mode="gray"``
 (v = (r + g + b) / 3 of (n, H, W, 3) pixels or rows of 3-byte pixels): the bytes then go
 through the whole stack as bytes - integer column sums into the pooled mean, the exact
@@ -83,10 +85,13 @@ class PCA:
             if X.device.type != "cuda":
                 X = X.to(torch.device("cuda", torch.cuda.current_device()))
             return X
-        if X.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"PCA.{what}: samples must be float32 or float64, got {X.dtype}")
+        if X.dtype not in (torch.float32, torch.float64, torch.bfloat16):
+            raise TypeError(f"PCA.{what}: samples must be float32, float64 or bfloat16, "
+                            f"got {X.dtype}")
         if X.dim() != 2:
             raise ValueError(f"PCA.{what}: samples must be 2-D (n, d), got {tuple(X.shape)}")
+        if X.dtype == torch.bfloat16:  # stays bf16 through the whole stack
+            return linalg.bf16_device_tensor(X, f"PCA.{what}")
         return linalg.require_device_tensor(X, f"PCA.{what}", keep_f64=True)
 
     def _all_reduce(self, v: torch.Tensor) -> torch.Tensor:

@@ -43,6 +43,10 @@ extern "C" {
  * deig_topk_sym_ex). */
 #define DEIG_F32 0
 #define DEIG_F64 1
+/* bf16 samples (deig_colsum, deig_syrk_shift, deig_syrk_centered): an element is the upper 16
+ * bits of the fp32 value, as torch.bfloat16 and __bf16 store it; alignment 2 bytes.  Widening
+ * is exact, so these entry points return the bits they return for the fp32 copy. */
+#define DEIG_BF16 2
 
 /* Library version, e.g. 0x000400 for 0.4.0.  A caller built against an older header
  * should compare it with the version it was built for before binding entry points
@@ -95,6 +99,33 @@ int deig_syrk_f32_ex(const float* X, int64_t n, int64_t d, int64_t ldx, float al
                      float* S, int64_t lds, int algo, void* ws, size_t ws_bytes, void* stream);
 size_t deig_syrk_workspace_ex(int64_t n, int64_t d, int algo);
 
+/* Covariance of bf16 samples taken as they are:  S = alpha X^T X,  or  S += alpha X^T X  with
+ * flags = DEIG_SYRK_ACCUMULATE (any other flag bit: DEIG_EINVAL).  No fp32 copy of X is made:
+ * the workspace holds a bf16 image of one row chunk in MFMA operand order and fp32 partials.
+ * X: n x d row-major bf16 (DEIG_BF16 elements), 16-byte aligned, n >= 1, d % 8 == 0 (d <=
+ * 32768), ldx % 8 == 0, ldx >= d; no element behind column d of a row is read.  S: fp32,
+ * 16-byte aligned, lds >= d, lds % 4 == 0; both triangles are written from one value, so S is
+ * bit-exactly symmetric (when accumulating, the lower triangle of the incoming S is the one
+ * that is read).
+ * Contract: a bf16 x bf16 product has 16 significant bits and is exact in fp32, so every
+ * product is exact (one v_mfma_f32_16x16x32_bf16 per fragment pair; no hi/lo split, no
+ * diagonal correction), and S differs from the exact sum only by the fp32 summation.  That
+ * is two-level: an MFMA accumulator takes at most 16384 rows (in K-steps of 32) before it is
+ * written out as a partial, and the partials (and the incoming S) are added in a fixed order:
+ * about (16384 / 32 + n / 16384) eps in the worst case relative to sum_r |x_ri x_rj|, random
+ * walk ~sqrt of that in practice.  Integer data whose partial sums stay below 2^24 give the
+ * exact result.  Inputs whose products underflow the fp32 normal range are outside the
+ * contract.
+ * Workspace: the query returns the recommended size.  Any workspace of at least
+ * deig_syrk_bf16_workspace(n', d) bytes for some 1 <= n' <= n is accepted and makes the call
+ * run in row chunks; a smaller one is DEIG_EWORKSPACE.  The workspace may hold anything on
+ * entry.  Asynchronous on `stream`: no allocation, no synchronisation, no float atomics;
+ * repeated calls give identical bits.  Argument errors are DEIG_EINVAL before any GPU work.
+ * Additive, like the uint8 entry points: probe for the symbols, deig_version() is unchanged. */
+int deig_syrk_bf16(const void* X, int64_t n, int64_t d, int64_t ldx, float alpha,
+                   float* S, int64_t lds, int flags, void* ws, size_t ws_bytes, void* stream);
+size_t deig_syrk_bf16_workspace(int64_t n, int64_t d);
+
 /* Mean-shifted covariance of float samples, float64 result (the reference's own
  * float64 data flow: distributed.py:169-173 grey values -> compute_sigma_hat_
  * :59-70):  S64 = alpha * X^T X  computed as
@@ -104,7 +135,7 @@ size_t deig_syrk_workspace_ex(int64_t n, int64_t d, int algo);
  * SYRK's rounding is then relative to the CENTRED data, not to the mean direction
  * that dominates an uncentered covariance of byte images (see shift.hip for the
  * measured effect on the top-k basis).  X: n x d row-major, element type xtype
- * (DEIG_F32 / DEIG_F64), row stride ldx elements, aligned to its element size.
+ * (DEIG_F32 / DEIG_F64 / DEIG_BF16), row stride ldx elements, aligned to its element size.
  * S64 (float64, lds64) and/or S (its fp32 rounding, lds) may be NULL (not both);
  * both triangles are written (bit-exact symmetry).
  * Workspace: deig_syrk_shift_workspace(n, d, xtype) (holds an fp32 copy of C). */
@@ -115,7 +146,7 @@ size_t deig_syrk_shift_workspace(int64_t n, int64_t d, int xtype);
 
 /* Column sums in double: sums[j] = sum_r X[r][j] (the first pass of deig_syrk_shift as an
  * entry point of its own; a multi-GPU centred fit all-reduces these into the pooled mean).
- * X: n x d row-major of element type xtype (DEIG_F32 / DEIG_F64), row stride ldx, aligned
+ * X: n x d row-major of element type xtype (DEIG_F32 / DEIG_F64 / DEIG_BF16), row stride ldx, aligned
  * to its element size; sums: d doubles on the device.  The rows are summed in a fixed
  * order (min(n, 128) row groups, then the groups in order), so the result is
  * deterministic.  Asynchronous on `stream`, no allocation, no synchronisation. */
@@ -523,6 +554,17 @@ int deig_pca_transform_u8(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, i
                           int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
                           void* stream);
 size_t deig_pca_transform_u8_workspace(int64_t n, int64_t d, int k);
+
+/* The same transform from bf16 samples (DEIG_BF16 elements), read once and never widened in
+ * memory: semantics, argument rules and accuracy notes are those of deig_pca_transform_f32,
+ * with X n x d row-major bf16, d % 8 == 0, ldx % 8 == 0 (elements), 16-byte aligned.  Each
+ * staged value is t = fl32((double)x - mean), rounded once; without a mean it is the exact
+ * widening.  Rows past n and features past d contribute exact zeros; no element behind column
+ * d of a row is read.  Workspace: the packed W image and the mean, padded to 64 features. */
+int deig_pca_transform_bf16(const void* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
+                            const float* W, int k, int64_t ldw, float* Y, int64_t ldy,
+                            float* resid, float* energy, void* ws, size_t ws_bytes, void* stream);
+size_t deig_pca_transform_bf16_workspace(int64_t n, int64_t d, int k);
 
 /* Building block of the solvers, exposed for direct testing / reuse:
  * C[M x N] = alpha * op(A) * B + beta * C  on fp32 MFMA (16x16x4), N % 16 == 0, N <= 256.
