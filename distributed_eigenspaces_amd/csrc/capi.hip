@@ -113,6 +113,36 @@ static int check_opts(const deig_solver_opts* o) {
   return DEIG_OK;
 }
 
+// The projector average with k > 128 deflates its locked blocks by fp32 skinny products with
+// V itself (solver.hip apply_op_plain: the operator is implicit, there is no matrix to fold
+// them into), which read V as a 16-byte aligned matrix with ldv % 4 == 0.  k alone decides
+// that, so the rule is checked before any GPU work.
+static int check_product_basis(const float* V, int64_t ldv, const char* what, const char* why) {
+  if (ldv % 4 != 0 || !aligned16(V))
+    return fail(DEIG_EINVAL, "%s: %s deflates locked pairs by products with V: V must be 16-byte "
+                             "aligned with ldv %% 4 == 0 (ldv=%lld)", what, why, (long long)ldv);
+  return DEIG_OK;
+}
+
+// The fp32-MFMA solver (sweep_algo = DEIG_SWEEP_FP32) reads S itself: float32 only.
+static int check_fp32_solver(const deig_solver_opts* o, int stype, const char* what) {
+  if (o && o->sweep_algo == DEIG_SWEEP_FP32 && stype != DEIG_F32)
+    return fail(DEIG_EINVAL, "%s: a float64 S needs the bf16x6 sweep (DEIG_SWEEP_AUTO)", what);
+  return DEIG_OK;
+}
+
+// Shape rules shared by deig_sym_apply_f32 and deig_sym_power_f32 (bf16x6 sweep).
+static int check_sweep_shape(int64_t d, int p, int64_t ldq, int64_t ldy, const void* Q,
+                             const void* Y, const char* what) {
+  if (d < 1 || p < 16 || p > 128 || p % 16 != 0)
+    return fail(DEIG_EINVAL, "%s: need d >= 1 and p in {16, 32, ..., 128} (p=%d)", what, p);
+  if (ldq < p || ldy < p)
+    return fail(DEIG_EINVAL, "%s: need ldq >= p and ldy >= p (ldq=%lld, ldy=%lld)", what,
+                (long long)ldq, (long long)ldy);
+  if (!Q || !Y) return fail(DEIG_EINVAL, "%s: null Q / Y", what);
+  return DEIG_OK;
+}
+
 static int syrk_resolve(int64_t n, int algo) {
   if (algo != DEIG_SYRK_AUTO) return algo;
   return n >= DEIG_SYRK_SPLIT_MIN_ROWS ? DEIG_SYRK_SPLIT3 : DEIG_SYRK_FP32;
@@ -242,6 +272,7 @@ int deig_topk_sym_ex(const void* S, int stype, int64_t d, int64_t lds, int k, in
   if (stype != DEIG_F32 && stype != DEIG_F64)
     return fail(DEIG_EINVAL, "topk: unknown element type %d", stype);
   if (int rc = check_matrix(S, stype, d, k, p, lds, "topk")) return rc;
+  if (int rc = check_fp32_solver(opts, stype, "topk")) return rc;
   SolveProblem pr{};
   pr.op.implicit = false;
   pr.op.S = S;
@@ -290,6 +321,7 @@ int deig_topk_sym_batch_ex(int W, const void* const* S, int stype, int64_t d, in
     return fail(DEIG_EINVAL, "topk_batch: unknown element type %d", stype);
   for (int i = 0; i < W; ++i)
     if (int rc = check_matrix(S[i], stype, d, k, p, lds, "topk_batch")) return rc;
+  if (int rc = check_fp32_solver(opts, stype, "topk_batch")) return rc;
   const size_t each = align_up(topk_ws(d, k, p, false, 0, opts, stype), 256);
   if (!ws || ws_bytes < (size_t)W * each)
     return fail(DEIG_EWORKSPACE, "topk_batch: workspace %zu bytes < required %zu", ws_bytes,
@@ -324,6 +356,8 @@ int deig_projavg_topk_ex(const float* Wt, int64_t d, int64_t mk, int64_t ldw, fl
   if (int rc = check_opts(opts)) return rc;
   if (!Wt || mk < 1 || ldw < d || ldw % 4 != 0 || !aligned16(Wt))
     return fail(DEIG_EINVAL, "projavg: Wt must be 16-byte aligned, mk >= 1, ldw >= d, ldw %% 4 == 0");
+  if (k > 128)  // block locking on the implicit operator
+    if (int rc = check_product_basis(V, ldv, "projavg", "k > 128")) return rc;
   SolveProblem pr{};
   pr.op.implicit = true;
   pr.op.stype = DEIG_F32;
@@ -382,6 +416,11 @@ int deig_sym_power_f32(const float* S, int64_t d, int64_t lds, float* Q, int p, 
   algo &= ~(DEIG_SWEEP_PREPARED | DEIG_SWEEP_ROUND_Q | DEIG_SWEEP_FAST | DEIG_SWEEP_HALF);
   if (algo != DEIG_SWEEP_AUTO && algo != DEIG_SWEEP_BF16X6)
     return fail(DEIG_EINVAL, "sym_power: algorithm %d has no fused chain (bf16x6 only)", algo);
+  if (int rc = check_sweep_shape(d, p, ldq, ldy, Q, Y, "sym_power")) return rc;
+  // the fused basis step (sweep.hip sweep_finish_kernel) moves Q and Y rows as float4
+  if (ldq % 4 != 0 || ldy % 4 != 0 || !aligned16(Q) || !aligned16(Y))
+    return fail(DEIG_EINVAL, "sym_power: Q and Y must be 16-byte aligned with ldq %% 4 == 0 and "
+                             "ldy %% 4 == 0 (ldq=%lld, ldy=%lld)", (long long)ldq, (long long)ldy);
   hipStream_t st = (hipStream_t)stream;
   if (!prepared) {
     const int rc = sweep_prepare(S, DEIG_F32, d, lds, p, ws, ws_bytes, st);
@@ -414,9 +453,19 @@ int deig_sym_apply_f32(const float* S, int64_t d, int64_t lds, const float* Q, i
                        int64_t ldq, float* Y, int64_t ldy, float alpha, int algo, void* ws,
                        size_t ws_bytes, void* stream) {
   g_err[0] = 0;
-  if (algo == DEIG_SWEEP_FP32)
+  if (algo == DEIG_SWEEP_FP32) {
+    // the skinny product's operand rules (skinny.hip skinny_launch), named for this entry point
+    if (d < 4 || d % 4 != 0 || lds < d || lds % 4 != 0 || !S || !aligned16(S))
+      return fail(DEIG_EINVAL, "sym_apply: DEIG_SWEEP_FP32 needs d %% 4 == 0 and a 16-byte aligned S "
+                               "with lds >= d, lds %% 4 == 0 (d=%lld, lds=%lld)", (long long)d,
+                  (long long)lds);
+    if (ldq < p || ldq % 4 != 0 || !Q || !aligned16(Q) || ldy < p || !Y)
+      return fail(DEIG_EINVAL, "sym_apply: DEIG_SWEEP_FP32 needs a 16-byte aligned Q with ldq >= p, "
+                               "ldq %% 4 == 0, and ldy >= p (ldq=%lld, ldy=%lld)", (long long)ldq,
+                  (long long)ldy);
     return skinny_launch(true, S, lds, Q, ldq, Y, ldy, d, p, d, alpha, 0.f,
                          static_cast<float*>(ws), ws_bytes, (hipStream_t)stream);
+  }
   const bool prepared = (algo & DEIG_SWEEP_PREPARED) != 0;
   const bool kernel_only = (algo & DEIG_SWEEP_KERNEL_ONLY) != 0;
   const int smode = (algo & DEIG_SWEEP_HALF)      ? kSweepHalf
@@ -427,6 +476,7 @@ int deig_sym_apply_f32(const float* S, int64_t d, int64_t lds, const float* Q, i
             DEIG_SWEEP_KERNEL_ONLY);
   if (algo != DEIG_SWEEP_AUTO && algo != DEIG_SWEEP_BF16X6)
     return fail(DEIG_EINVAL, "sym_apply: unknown algorithm %d", algo);
+  if (int rc = check_sweep_shape(d, p, ldq, ldy, Q, Y, "sym_apply")) return rc;
   if (!prepared) {
     const int rc = sweep_prepare(S, DEIG_F32, d, lds, p, ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;

@@ -330,8 +330,9 @@ struct Operator {
   const float* Wt;  // implicit: scale * Wt^T Wt
   int64_t mk, ldw;
   float scale;
-  // applied on top of the base operator (image: folded in by sweep_prepare;
-  // plain products: applied after each product): + shift I - Vd diag(lamd) Vd^T
+  // applied on top of the base operator (explicit S: folded in, in double, by sweep_prepare
+  // or into the fp32 sweep's copy of S; implicit: applied as products after each product):
+  // + shift I - Vd diag(lamd) Vd^T
   double shift;
   const float* Vd;
   int64_t ldvd;

@@ -63,10 +63,11 @@ struct SolverWs {
   size_t slab_bytes;
   void* sweep_ws;  // bf16x6 sweep image (explicit S only)
   size_t sweep_bytes;
+  float* Sdef;     // d x d: the shifted / deflated S of the fp32 sweep (explicit S, no image)
 };
 
 // p: the widest block subspace, kb: the most pairs one block targets (<= p), k:
-// all pairs (locked ones are deflated by plain products when there is no image).
+// all pairs (the implicit operator deflates its locked ones by plain products).
 SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int64_t mk,
                       bool image, size_t* total) {
   Carve c(ws, cap);
@@ -84,7 +85,7 @@ SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int
   w.rr.info = c.take<int>(16);
   w.Zt = mk > 0 ? c.take<float>((size_t)mk * p) : nullptr;
   w.T = c.take<float>((size_t)d * p);
-  w.Tdef = image ? nullptr : c.take<float>((size_t)k * p);
+  w.Tdef = mk > 0 ? c.take<float>((size_t)k * p) : nullptr;
   w.rq = mk > 0 ? nullptr : c.take<char>(rq_workspace_bytes(d, k));
   size_t sb = skinny_workspace_bytes(2 * p, 2 * p, d);  // Gram
   auto need = [&](int64_t M, int64_t N, int64_t K) {
@@ -97,7 +98,7 @@ SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int
   } else if (!image) {
     need(d, p, d);  // S Q
   }
-  if (!image) {  // plain-product deflation: Vd^T Q and Vd T
+  if (mk > 0) {  // plain-product deflation of the implicit operator: Vd^T Q and Vd T
     need(k, p, d);
     need(d, p, k);
   }
@@ -109,6 +110,7 @@ SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int
     w.sweep_bytes = sweep_workspace_bytes(d, p);
     w.sweep_ws = c.take<char>(w.sweep_bytes);
   }
+  w.Sdef = (!image && mk == 0) ? c.take<float>((size_t)d * d) : nullptr;
   *total = c.off;
   return w;
 }
@@ -132,14 +134,45 @@ __global__ __launch_bounds__(256) void neg_scale_rows_kernel(float* __restrict__
   T[idx] *= -lam[idx / p];
 }
 
-// Y = A Q without a sweep image: the fp32 skinny product (explicit S) or the
-// implicit projector average Wt^T (Wt Q) (the server), then the shift and the
-// deflation of the locked pairs as products with Vd.
+// out (d x d, row stride d) = S + shift I - V_D diag(lam_D) V_D^T: the operator of the fp32
+// sweep once pairs are locked or S is shifted.  Formed in double from S's own values and
+// rounded to fp32 once, as sweep_prepare_kernel forms the bf16x6 image: the deflated entries
+// carry fp32 rounding relative to their own size.  (Deflating by fp32 products S q - V_D
+// lam_D V_D^T q instead leaves the rounding of S q at eps |lambda_1|: a block 1000 times
+// below a locked pair stalled at a residual of 2e-5 of its own scale.)  v_i v_j is exact in
+// double, so both triangles get the same bits.  V_D is read by element: any ldv.
+__global__ __launch_bounds__(256) void deflate_copy_kernel(const float* __restrict__ S, int64_t lds,
+                                                           int64_t d, const float* __restrict__ Vd,
+                                                           int64_t ldv, const float* __restrict__ lamd,
+                                                           int r, double shift,
+                                                           float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= d * d) return;
+  const int64_t i = idx / d, j = idx - i * d;
+  double s = (double)S[i * lds + j];
+  if (i == j) s += shift;
+  for (int q = 0; q < r; ++q) {
+    const float* vq = Vd + (int64_t)q * ldv;
+    s = fma(-(double)lamd[q], (double)vq[i] * (double)vq[j], s);
+  }
+  out[idx] = (float)s;
+}
+
+// The fp32 sweep reads the shifted / deflated copy instead of S (Solver::prepare wrote it).
+bool folded_operator(const Operator& op, const SolverWs& w) {
+  return !op.implicit && w.Sdef && (op.r > 0 || op.shift != 0.0);
+}
+
+// Y = A Q without a sweep image: the fp32 skinny product (explicit S, or its shifted /
+// deflated copy) or the implicit projector average Wt^T (Wt Q) (the server), followed for
+// that one by the shift and the deflation of the locked pairs as products with Vd.
 int apply_op_plain(const Operator& op, const SolverWs& w, int64_t d, int p, hipStream_t st) {
   float* Q = w.rr.Z;
   float* Y = w.rr.Z + p;
   const int64_t ld = 2 * p;
   int rc;
+  if (folded_operator(op, w))
+    return skinny_launch(true, w.Sdef, d, Q, ld, Y, ld, d, p, d, 1.f, 0.f, w.slab, w.slab_bytes, st);
   if (!op.implicit) {
     rc = skinny_launch(true, static_cast<const float*>(op.S), op.lds, Q, ld, Y, ld, d, p, d, 1.f,
                        0.f, w.slab, w.slab_bytes, st);
@@ -574,11 +607,18 @@ struct Solver {
     return DEIG_OK;
   }
 
-  // (Re)build the sweep image of the current operator (explicit S only).
+  // (Re)build the current operator's sweep image or, for the fp32 sweep, its shifted /
+  // deflated copy (explicit S only).
   int prepare(int pb_) {
-    if (!w.sweep_ws) return DEIG_OK;
-    return sweep_prepare(op.S, op.stype, d, op.lds, pb_, w.sweep_ws, w.sweep_bytes, st, op.Vd,
-                         op.ldvd, op.lamd, op.r, op.shift);
+    if (w.sweep_ws)
+      return sweep_prepare(op.S, op.stype, d, op.lds, pb_, w.sweep_ws, w.sweep_bytes, st, op.Vd,
+                           op.ldvd, op.lamd, op.r, op.shift);
+    if (!folded_operator(op, w)) return DEIG_OK;
+    hipLaunchKernelGGL(deflate_copy_kernel, dim3((unsigned)cdiv(d * d, 256)), dim3(256), 0, st,
+                       static_cast<const float*>(op.S), op.lds, d, op.Vd, op.ldvd, op.lamd, op.r,
+                       op.shift, w.Sdef);
+    DEIG_HIP_CHECK(hipGetLastError());
+    return DEIG_OK;
   }
 };
 
@@ -968,10 +1008,10 @@ bool same_layout(const SolverWs& a, const SolverWs& b, int64_t* off) {
   *off = o;
   const void* pa[] = {a.rr.C, a.rr.Linv, a.rr.Wtmp, a.rr.W, a.rr.lam, a.rr.cs, a.rr.qs,
                       a.rr.resid_part, a.rr.resid, a.rr.info, a.Zt, a.T, a.Tdef, a.rq, a.slab,
-                      a.sweep_ws};
+                      a.sweep_ws, a.Sdef};
   const void* pb[] = {b.rr.C, b.rr.Linv, b.rr.Wtmp, b.rr.W, b.rr.lam, b.rr.cs, b.rr.qs,
                       b.rr.resid_part, b.rr.resid, b.rr.info, b.Zt, b.T, b.Tdef, b.rq, b.slab,
-                      b.sweep_ws};
+                      b.sweep_ws, b.Sdef};
   for (size_t i = 0; i < sizeof(pa) / sizeof(pa[0]); ++i) {
     if (!pa[i] != !pb[i]) return false;
     if (pa[i] && dl(pb[i], pa[i]) != o) return false;

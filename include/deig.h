@@ -279,7 +279,14 @@ int deig_default_subspace(int64_t d, int k);
 
 /* One subspace-iteration sweep Y = alpha * S Q  (S symmetric d x d row-major, lds;
  * Q d x p row-major, ldq; Y d x p row-major, ldy; p % 16 == 0, 16 <= p <= 128).
- * The S*Q product inside deig_topk_sym_f32, exposed for measurement and reuse. */
+ * The S*Q product inside deig_topk_sym_f32, exposed for measurement and reuse.
+ * Leading dimensions and alignment, all checked before any GPU work (DEIG_EINVAL):
+ *  S: 16-byte aligned, lds >= d, lds % 4 == 0 (both algorithms);
+ *  DEIG_SWEEP_BF16X6 / AUTO: any ldq >= p and ldy >= p, element alignment of Q and Y
+ *    (ROUND_Q / FAST / HALF write the rounded Q back through ldq);
+ *  DEIG_SWEEP_FP32: d % 4 == 0, Q 16-byte aligned with ldq % 4 == 0; any ldy >= p.
+ * No element behind column d of an S row or column p of a Q row is read, none behind
+ * column p of a Y (or Q) row is written. */
 int deig_sym_apply_f32(const float* S, int64_t d, int64_t lds, const float* Q, int p,
                        int64_t ldq, float* Y, int64_t ldy, float alpha, int algo, void* ws,
                        size_t ws_bytes, void* stream);
@@ -294,7 +301,10 @@ size_t deig_sym_apply_workspace(int64_t d, int p, int algo);
  * (ROUND_Q / FAST: every Q rounded to two bf16 pieces as for deig_sym_apply_f32).
  * algo: DEIG_SWEEP_BF16X6 / AUTO with the PREPARED / ROUND_Q / FAST flags; the
  * workspace is deig_sym_apply_workspace's.  Extends the sweep entry point (no
- * reference counterpart: the reference solves with LAPACK, distributed.py:22-29). */
+ * reference counterpart: the reference solves with LAPACK, distributed.py:22-29).
+ * The fused step moves rows of Q and Y as 16-byte vectors: Q and Y must be 16-byte
+ * aligned with ldq % 4 == 0 and ldy % 4 == 0 (ldq, ldy >= p; S as for
+ * deig_sym_apply_f32); anything else is DEIG_EINVAL before any GPU work. */
 int deig_sym_power_f32(const float* S, int64_t d, int64_t lds, float* Q, int p, int64_t ldq,
                        float* Y, int64_t ldy, const float* cs, int steps, int algo, void* ws,
                        size_t ws_bytes, void* stream);
@@ -351,7 +361,15 @@ void deig_solver_opts_init(deig_solver_opts* opts);
  * within 4 tol / 2e-6 of it, the fp32 floor); returns DEIG_NOT_CONVERGED after
  * max_sweeps sweeps (per block), or earlier when it stalls above that floor.
  * Outputs: V (d x k col-major, ldv), evals (k, ascending), *sweeps_out,
- * *resid_out = final max relative residual (host pointers, may be NULL). */
+ * *resid_out = final max relative residual (host pointers, may be NULL).
+ * Leading dimensions: any ldv >= d and any ldq0 >= d with element alignment of V and Q0
+ * (nothing behind row d of a column is read or written; an ldv % 4 != 0 or a V that is
+ * not 16-byte aligned only moves the final Rayleigh quotients of a float32 S from the
+ * f64-MFMA kernel to the plain one: same accuracy, not the same bits).  That holds for
+ * deig_solver_opts.sweep_algo = DEIG_SWEEP_FP32 as well: it has no image of S to deflate,
+ * so it iterates on a d x d fp32 copy of S - V_D L_D V_D^T (+ sigma I) in the workspace,
+ * formed in double like the image (a float64 S with that option is DEIG_EINVAL before any
+ * GPU work). */
 int deig_topk_sym_f32(const float* S, int64_t d, int64_t lds, int k, int p,
                       int max_sweeps, float tol, const float* Q0, int k0, int64_t ldq0,
                       float* V, int64_t ldv, float* evals, int* sweeps_out,
@@ -414,7 +432,11 @@ int deig_topk_sym_batch(int W, const void* const* S, int stype, int64_t d, int64
 
 size_t deig_projavg_workspace(int64_t d, int64_t mk, int k, int p);
 /* With options (k > 128: block locking with the locked pairs deflated by products
- * with them - the operator stays implicit). */
+ * with them - the operator stays implicit).  Wt: 16-byte aligned, ldw >= d, ldw % 4 == 0,
+ * d % 4 == 0, d >= 16.  V: any ldv >= d and element alignment for k <= 128; for k > 128
+ * the products with the locked pairs read V itself, which must then be 16-byte aligned
+ * with ldv % 4 == 0 (DEIG_EINVAL before any GPU work otherwise; deig_projavg_topk_f32
+ * alike).  Q0: any ldq0 >= d. */
 int deig_projavg_topk_ex(const float* Wt, int64_t d, int64_t mk, int64_t ldw, float scale, int k,
                          int p, int max_sweeps, float tol, const float* Q0, int k0, int64_t ldq0,
                          float* V, int64_t ldv, float* evals, int* sweeps_out, float* resid_out,
@@ -464,7 +486,10 @@ size_t deig_subspace_dist_workspace(int64_t d, int k);
 /* One mini-batch Oja step (online variant, BASELINE.json config 4; not in the
  * reference - parity unpinned):  V <- orth(V + eta/b * Xb^T (Xb V)).
  * Xb is b x d row-major (ldx), V is d x k column-major (ldv), updated in place.
- * k <= 64.  Orthonormalisation: Cholesky-QR2. */
+ * k <= 64.  Orthonormalisation: Cholesky-QR2.
+ * Requires d % 4 == 0, Xb 16-byte aligned with ldx >= d, ldx % 4 == 0; any ldv >= d and
+ * element alignment of V (the same for deig_oja_steps_f32 / deig_oja_steps_ex).  Nothing
+ * behind column d of an Xb row is read, nothing behind row d of a V column is touched. */
 int deig_oja_step_f32(const float* Xb, int64_t b, int64_t d, int64_t ldx, float eta,
                       float* V, int k, int64_t ldv, void* ws, size_t ws_bytes,
                       void* stream);
@@ -509,7 +534,9 @@ int deig_oja_error(const void* ws, size_t ws_bytes, int64_t b, int64_t d, int k,
 /* Projection onto an estimated eigenspace: Y = X W.
  * Replaces the notebook's  online_distributed_PCA = lambda X: X @ matrix_w
  * (Online Distributed PCA.ipynb raw line 345).  X: n x d row-major (ldx), W: d x k
- * column-major (ldw, the solvers' V), Y: n x k row-major (ldy).  k <= 256. */
+ * column-major (ldw, the solvers' V), Y: n x k row-major (ldy).  k <= 256.
+ * Requires d % 4 == 0, X 16-byte aligned with ldx >= d, ldx % 4 == 0; any ldw >= d and
+ * any ldy >= k with element alignment of W and Y. */
 int deig_project_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const float* W, int k,
                      int64_t ldw, float* Y, int64_t ldy, void* ws, size_t ws_bytes,
                      void* stream);
