@@ -18,7 +18,8 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
                      copy (sigma_hat dispatches to it); column_sums, sigma_hat_centered,
                      pca_transform, the estimator and PCA take bfloat16 without widening it
   * oja_step(s)    - mini-batch Oja (online variant, config 4); streaming.StreamingOja
-                     adds the periodic all-gather / server solve / broadcast
+                     adds the periodic all-gather / server solve / broadcast; bfloat16
+                     batches are read as bfloat16 (two-product kernels, no float32 copy)
 
 Drop-in modules: ``distributed`` (Node / SlaveNode / MasterNode / run_* / main),
 ``my_threading`` (Slave) and ``notebook`` (make_batches, top_k_eigenvectors,

@@ -8,7 +8,11 @@
 // operand image (T's for TN, V's for the next batch's NN); the resident v4
 // (oja_blk_kernel, config 4's shape) runs a whole run of batches in one launch with
 // each workgroup's block of Xb held in registers - Xb read once per batch.
+// bf16 samples (deig_oja_steps_bf16) run the two-pass kernels instantiated on the sample
+// type: a bf16 value is its own hi piece, so two MFMAs per fragment pair instead of three
+// and half the bytes of Xb, with the bits of the float kernels on the widened samples.
 #include <algorithm>
+#include <type_traits>
 
 #include "bf16_split.hpp"
 #include "deig_internal.hpp"
@@ -241,6 +245,75 @@ __global__ __launch_bounds__(256) void trsm_img_kernel(const float* __restrict__
   }
 }
 
+// The sample type of the two passes: float samples are split into hi / lo bf16 pieces in
+// registers (three MFMAs per fragment pair); a bf16 sample (OjaBf16: the upper 16 bits of
+// the float, as torch.bfloat16 stores it) IS its hi piece and its lo piece is exactly zero,
+// so the third MFMA (lo hi) of the float kernels would add an exact zero and is left out:
+// the same k-steps in the same order, hence the bits of the float kernels on the widened
+// samples, from half the bytes.
+typedef __bf16 OjaBf16;
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// NN operand: a lane's 8 consecutive features of one row (p: the row, k: first feature,
+// clamped so that nothing behind column d is read) and its A fragments.
+template <typename XT>
+struct OjaRow8;
+template <>
+struct OjaRow8<float> {
+  static constexpr bool kLo = true;
+  f32x4 a, b;
+  __device__ __forceinline__ void load(const float* p, int k, int d) {
+    a = *reinterpret_cast<const f32x4*>(p + min(k, d - 4));
+    b = *reinterpret_cast<const f32x4*>(p + min(k + 4, d - 4));
+  }
+  __device__ __forceinline__ void frags(bf16x8& hi, bf16x8& lo) const { split8(a, b, hi, lo); }
+};
+template <>
+struct OjaRow8<OjaBf16> {  // one 16-byte load, already the fragment (d % 8 == 0)
+  static constexpr bool kLo = false;
+  u32x4 a;
+  __device__ __forceinline__ void load(const OjaBf16* p, int k, int d) {
+    a = *reinterpret_cast<const u32x4*>(p + min(k, d - 8));
+  }
+  __device__ __forceinline__ void frags(bf16x8& hi, bf16x8&) const { hi = __builtin_bit_cast(bf16x8, a); }
+};
+
+// TN operand: a lane's 4 consecutive features of one row, read back as floats for the
+// [feature][row] transpose region (bf16: one 8-byte load, widened on the way in).
+template <typename XT>
+struct OjaSeg4;
+template <>
+struct OjaSeg4<float> {
+  f32x4 v;
+  __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const f32x4*>(p); }
+  __device__ __forceinline__ float get(int e) const { return v[e]; }
+};
+template <>
+struct OjaSeg4<OjaBf16> {
+  u32x2 v;
+  __device__ __forceinline__ void load(const OjaBf16* p) { v = *reinterpret_cast<const u32x2*>(p); }
+  __device__ __forceinline__ float get(int e) const { return (e & 1) ? hi_f(v[e >> 1]) : lo_f(v[e >> 1]); }
+};
+// The A fragments of 8 transposed values: split for floats; widened bf16 values pack back
+// exactly (round to nearest of a bf16 value is the value).
+template <typename XT>
+__device__ __forceinline__ void oja_frags8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
+  if constexpr (OjaRow8<XT>::kLo) {
+    split8(a, b, hi, lo);
+  } else {
+    hi = __builtin_bit_cast(bf16x8, u32x4{cvt2(a[0], a[1]), cvt2(a[2], a[3]), cvt2(b[0], b[1]), cvt2(b[2], b[3])});
+  }
+}
+// acc += a b from the pieces: hi hi + hi lo (+ lo hi when a has a lo piece), in that order.
+template <bool LO>
+__device__ __forceinline__ f32x4 oja_mfma(const bf16x8& ahi, const bf16x8& alo, const bf16x8& bhi,
+                                          const bf16x8& blo, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc, 0, 0, 0);
+  if constexpr (LO) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc, 0, 0, 0);
+  return acc;
+}
+
 constexpr int kOjaPF = 4;  // prefetch depth of the NN / TN passes (k-steps)
 
 // NN: T = Xb V (b x kp), written as the TN pass's B-operand image (img_kernel's
@@ -250,9 +323,10 @@ constexpr int kOjaPF = 4;  // prefetch depth of the NN / TN passes (k-steps)
 // lane l holds row r0 + (l & 15), features 32 ks + 8 (l >> 4) .. + 7 (two float4
 // loads; the 16 rows x 128 B of a wave-instruction pair are whole lines), split to
 // hi / lo in registers; B from the V image (img_kernel), L2-resident.  Loads run
-// PF k-steps ahead of the MFMAs (register ring).
-template <int NB>
-__global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X, int64_t ldx, int64_t b,
+// PF k-steps ahead of the MFMAs (register ring).  XT = OjaBf16: the lane's 8 features
+// are one 16-byte load that is the fragment itself (OjaRow8), features clamped to d - 8.
+template <int NB, typename XT>
+__global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, int64_t ldx, int64_t b,
                                                      int d, int nks, const u32x4* __restrict__ vimg,
                                                      u32x4* __restrict__ timg) {
   constexpr int PF = kOjaPF;
@@ -266,19 +340,17 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X
   // loads are never predicated (the compiler's counted waits stay deep): rows >= b
   // and features >= d read clamped in-range addresses; the V image is zero past d
   // and rows >= b are zeroed below
-  const float* xr = X + (row < b ? row : b - 1) * ldx;
+  const XT* xr = X + (row < b ? row : b - 1) * ldx;
   const int NKS = nks;
   const int per = (nks + 7) / 8;
   const int ks0 = wave * per, ks1 = min(nks, ks0 + per);
   f32x4 acc[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 xa[PF], xb[PF];
+  OjaRow8<XT> xs[PF];
   u32x4 bh[PF][NB], bl[PF][NB];
   auto load = [&](int ks, int slot) {
-    const int k = 32 * ks + 8 * (lane >> 4);
-    xa[slot] = *reinterpret_cast<const f32x4*>(xr + min(k, d - 4));
-    xb[slot] = *reinterpret_cast<const f32x4*>(xr + min(k + 4, d - 4));
+    xs[slot].load(xr, 32 * ks + 8 * (lane >> 4), d);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bh[slot][nb] = vimg[img_index(ks, nb, 0, lane, NB)];
@@ -287,14 +359,12 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X
   };
   auto step = [&](int u) {
     bf16x8 ahi, alo;
-    split8(xa[u], xb[u], ahi, alo);
+    xs[u].frags(ahi, alo);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
       const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
-      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc[nb], 0, 0, 0);
-      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc[nb], 0, 0, 0);
-      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc[nb], 0, 0, 0);
+      acc[nb] = oja_mfma<OjaRow8<XT>::kLo>(ahi, alo, bhi, blo, acc[nb]);
     }
   };
 #pragma unroll
@@ -353,9 +423,13 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const float* __restrict__ X
 // 32 rows x 16 features with float4 loads (whole 64-B row segments) and transposes
 // them through its own LDS region ([feature][row], TS floats a row); B is the T
 // image (img_kernel).  An 8-feature group of the V image never straddles two
-// blocks (16 | 32), so each block writes its own image entries.
-template <int NB>
-__global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X, int64_t ldx, int64_t b,
+// blocks (16 | 32), so each block writes its own image entries.  XT = OjaBf16: the
+// same block shape and lane mapping with 8-byte loads (a lane's 4 features; a row
+// segment of the block is 32 B), widened on the way into the same LDS region, so the
+// region, the reads and every sum are the float kernel's; the blocks of one 128-B line
+// (4 instead of 2) are consecutive logical blocks, which xcd_logical keeps on one XCD.
+template <int NB, typename XT>
+__global__ __launch_bounds__(512) void oja_tn_kernel(const XT* __restrict__ X, int64_t ldx, int64_t b,
                                                      int d, int nkr, const u32x4* __restrict__ timg,
                                                      float c, float* __restrict__ V,
                                                      u32x4* __restrict__ vimg) {
@@ -372,7 +446,7 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X
   const int fl = 4 * (lane & 3);  // this lane's 4 features (load mapping)
   // unpredicated loads (see oja_nn_kernel): features >= d and rows >= b read clamped
   // in-range addresses; their products are dropped (f >= d) or meet zero T rows
-  const float* xb_ = X + min(f0 + fl, d - 4);
+  const XT* xb_ = X + min(f0 + fl, d - 4);
   const int NKS = nkr;
   const int per = (nkr + 7) / 8;
   const int ks0 = wave * per, ks1 = min(nkr, ks0 + per);
@@ -383,12 +457,12 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X
   // loads run PF k-steps (32 rows each) ahead of their use (register ring): one
   // k-step in flight per wave was latency-bound (16 KiB per CU)
   constexpr int PF = kOjaPF;
-  f32x4 xa[PF], xb[PF];
+  OjaSeg4<XT> xa[PF], xb[PF];
   u32x4 bh[PF][NB], bl[PF][NB];
   auto load = [&](int ks, int slot) {
     const int64_t r = 32 * (int64_t)ks + (lane >> 2);
-    xa[slot] = *reinterpret_cast<const f32x4*>(xb_ + min(r, b - 1) * ldx);
-    xb[slot] = *reinterpret_cast<const f32x4*>(xb_ + min(r + 16, b - 1) * ldx);
+    xa[slot].load(xb_ + min(r, b - 1) * ldx);
+    xb[slot].load(xb_ + min(r + 16, b - 1) * ldx);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bh[slot][nb] = timg[img_index(ks, nb, 0, lane, NB)];
@@ -399,20 +473,18 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const float* __restrict__ X
   auto step = [&](int u) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      T[(fl + e) * TS + rr] = xa[u][e];
-      T[(fl + e) * TS + rr + 16] = xb[u][e];
+      T[(fl + e) * TS + rr] = xa[u].get(e);
+      T[(fl + e) * TS + rr + 16] = xb[u].get(e);
     }
     const f32x4 a0 = *reinterpret_cast<const f32x4*>(T + (lane & 15) * TS + 8 * (lane >> 4));
     const f32x4 a1 = *reinterpret_cast<const f32x4*>(T + (lane & 15) * TS + 8 * (lane >> 4) + 4);
     bf16x8 ahi, alo;
-    split8(a0, a1, ahi, alo);
+    oja_frags8<XT>(a0, a1, ahi, alo);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
       const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
-      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bhi, acc[nb], 0, 0, 0);
-      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc[nb], 0, 0, 0);
-      acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc[nb], 0, 0, 0);
+      acc[nb] = oja_mfma<OjaRow8<XT>::kLo>(ahi, alo, bhi, blo, acc[nb]);
     }
   };
 #pragma unroll
@@ -992,22 +1064,21 @@ hipError_t launch_oja_blk(int nks, const OjaBlk& a, hipStream_t st) {
   }
 }
 
-int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
-                     float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
-                     hipStream_t st, int algo) {
-  DEIG_REQUIRE(nb >= 1 && b >= 1 && d >= 4 && d % 4 == 0,
-               "oja: need nb >= 1, b >= 1 and d %% 4 == 0");
-  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "oja: need 1 <= k <= min(64, d)");
-  DEIG_REQUIRE(ldx >= d && ldx % 4 == 0 && ldv >= d, "oja: bad leading dims");
-  DEIG_REQUIRE(orth_every >= 1, "oja: orth_every must be >= 1");
-  DEIG_REQUIRE(algo == DEIG_OJA_AUTO || algo == DEIG_OJA_TWO_PASS || algo == DEIG_OJA_RESIDENT,
-               "oja: unknown algo %d", algo);
+// The body of both entry points (arguments checked by the caller).  XT = OjaBf16 runs
+// the two-pass kernels only: it never asks for the CU count or the occupancy, never
+// launches the resident kernel, and so never sets the timeout word it clears.
+template <typename XT>
+int oja_steps_run(const XT* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta, float* V,
+                  int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes, hipStream_t st,
+                  int algo) {
+  constexpr bool kF32 = std::is_same<XT, float>::value;
   const int kp = (int)cdiv(k, 16) * 16;
   size_t total = 0;
   OjaWs o = carve_oja(ws, ws_bytes, b, d, kp, &total);
   if (!ws || total > ws_bytes)
     return fail(DEIG_EWORKSPACE, "oja: workspace %zu < %zu", ws_bytes, total);
-  bool blk = algo != DEIG_OJA_TWO_PASS && oja_blk_eligible(b, d, ldx, kp);
+  bool blk = false;
+  if constexpr (kF32) blk = algo != DEIG_OJA_TWO_PASS && oja_blk_eligible(b, d, ldx, kp);
   if (algo == DEIG_OJA_RESIDENT && !blk)
     return fail(DEIG_EINVAL, "oja: the resident path needs b = 4096, d = 512 c <= 3072, k <= 32 "
                              "and %d CUs (got b %lld, d %lld, k %d)", OB_G, (long long)b, (long long)d, k);
@@ -1034,7 +1105,7 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
   // the last one is CholQR2
   for (int64_t i0 = 0; i0 < nb;) {
     const int64_t i1 = std::min(nb, (i0 / orth_every + 1) * orth_every);
-    if (blk) {
+    if constexpr (kF32) if (blk) {
       // zeroed once per call: each launch leaves them at zero for the next
       if (i0 == 0) DEIG_HIP_CHECK(hipMemsetAsync(o.cnt, 0, OB_CNT_BYTES, st));
       OjaBlk a;
@@ -1068,16 +1139,16 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
     }
     if (!blk) {
       for (int64_t i = i0; i < i1; ++i) {
-        const float* Xb = X + i * b * ldx;
+        const XT* Xb = X + i * b * ldx;
         // T = Xb V (as the TN pass's operand image, every row of its nkr k-steps
         // written, zeros past b), then V += eta/b Xb^T T (and V's image)
         switch (NB) {
 #define DEIG_OJA_NB(x)                                                                           \
   case x:                                                                                        \
-    hipLaunchKernelGGL(oja_nn_kernel<x>, dim3((unsigned)(2 * nkr)), dim3(512), 0, st, Xb, ldx, b, \
-                       (int)d, nks, o.vimg, o.timg);                                             \
-    hipLaunchKernelGGL(oja_tn_kernel<x>, dim3((unsigned)cdiv(d, 16)), dim3(512), 0, st, Xb, ldx, b, \
-                       (int)d, nkr, o.timg, eta / (float)b, cur, o.vimg);                        \
+    hipLaunchKernelGGL((oja_nn_kernel<x, XT>), dim3((unsigned)(2 * nkr)), dim3(512), 0, st, Xb, ldx, \
+                       b, (int)d, nks, o.vimg, o.timg);                                          \
+    hipLaunchKernelGGL((oja_tn_kernel<x, XT>), dim3((unsigned)cdiv(d, 16)), dim3(512), 0, st, Xb, \
+                       ldx, b, (int)d, nkr, o.timg, eta / (float)b, cur, o.vimg);                \
     break;
           DEIG_OJA_NB(1) DEIG_OJA_NB(2) DEIG_OJA_NB(3) DEIG_OJA_NB(4)
 #undef DEIG_OJA_NB
@@ -1098,6 +1169,42 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
                      kp, V, ldv, o.err);
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
+}
+
+int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
+                     float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
+                     hipStream_t st, int algo) {
+  DEIG_REQUIRE(nb >= 1 && b >= 1 && d >= 4 && d % 4 == 0,
+               "oja: need nb >= 1, b >= 1 and d %% 4 == 0");
+  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "oja: need 1 <= k <= min(64, d)");
+  DEIG_REQUIRE(ldx >= d && ldx % 4 == 0 && ldv >= d, "oja: bad leading dims");
+  DEIG_REQUIRE(orth_every >= 1, "oja: orth_every must be >= 1");
+  DEIG_REQUIRE(algo == DEIG_OJA_AUTO || algo == DEIG_OJA_TWO_PASS || algo == DEIG_OJA_RESIDENT,
+               "oja: unknown algo %d", algo);
+  return oja_steps_run(X, nb, b, d, ldx, eta, V, k, ldv, orth_every, ws, ws_bytes, st, algo);
+}
+
+// bf16 samples as they are (include/deig.h deig_oja_steps_bf16): the two-pass kernels'
+// OjaBf16 instantiations, everything else of the call shared with the float path.
+int oja_steps_bf16_launch(const void* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
+                          float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
+                          hipStream_t st) {
+  DEIG_REQUIRE(nb >= 1, "oja_bf16: nb must be >= 1 (got %lld)", (long long)nb);
+  DEIG_REQUIRE(b >= 1, "oja_bf16: b must be >= 1 (got %lld)", (long long)b);
+  DEIG_REQUIRE(d >= 8 && d % 8 == 0, "oja_bf16: d must be a multiple of 8, at least 8 (got %lld)",
+               (long long)d);
+  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "oja_bf16: need 1 <= k <= min(64, d) (got k=%d, d=%lld)",
+               k, (long long)d);
+  DEIG_REQUIRE(ldx >= d, "oja_bf16: ldx must be >= d");
+  DEIG_REQUIRE(ldx % 8 == 0, "oja_bf16: ldx must be a multiple of 8 elements");
+  DEIG_REQUIRE(ldv >= d, "oja_bf16: ldv must be >= d");
+  DEIG_REQUIRE(orth_every >= 1, "oja_bf16: orth_every must be >= 1 (got %d)", orth_every);
+  DEIG_REQUIRE(X && V, "oja_bf16: X and V must not be NULL");
+  DEIG_REQUIRE(aligned16(X), "oja_bf16: X must be 16-byte aligned");
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(V) % sizeof(float) == 0,
+               "oja_bf16: V must be aligned to its element size");
+  return oja_steps_run(static_cast<const OjaBf16*>(X), nb, b, d, ldx, eta, V, k, ldv, orth_every, ws,
+                       ws_bytes, st, DEIG_OJA_TWO_PASS);
 }
 
 // The timeout word of the last oja_steps_launch on this workspace (set by a resident

@@ -904,8 +904,13 @@ def oja_step(Xb: torch.Tensor, V: torch.Tensor, eta: float) -> torch.Tensor:
     """In-place mini-batch Oja update V <- orth(V + eta/b Xb^T Xb V) (config 4).
 
     Not in the reference (parity unpinned).  V: (d, k) column-major float32
-    (as returned by topk_eigh), k <= 64.  Returns V.
+    (as returned by topk_eigh), k <= 64.  Returns V.  A bfloat16 Xb is consumed as
+    bfloat16 under the rules of ``oja_steps`` (no float32 copy, and the call stays
+    asynchronous: that route cannot time out).
     """
+    xb16 = _oja_bf16_samples(Xb, "auto", "oja_step")
+    if xb16 is not None:
+        return _oja_steps_bf16(xb16, V, eta, xb16.shape[0], 1, 1, "Xb")
     Xb = _rowmajor_4(require_device_tensor(Xb, "oja_step"), "Xb")
     b, d = Xb.shape
     k = _oja_basis(V, Xb, "Xb")
@@ -923,6 +928,34 @@ def _oja_basis(V: torch.Tensor, X: torch.Tensor, xname: str) -> int:
             or V.device != X.device:
         raise ValueError(f"V must be a (d, k) column-major float32 tensor on {xname}'s device")
     return V.shape[1]
+
+
+def _oja_bf16_samples(X, algo: str, name: str) -> torch.Tensor | None:
+    """The bfloat16 samples of an Oja call as ``deig_oja_steps_bf16`` takes them, or None
+    when the call goes the float32 route: not bfloat16, ``algo="resident"``, or a view the
+    entry point cannot read in place (not 2-D with unit column stride, d % 8 != 0, a row
+    stride % 8 != 0, a base that is not 16-byte aligned)."""
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.bfloat16 or algo not in ("auto", "two_pass"):
+        return None
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 8 or X.shape[1] % 8:
+        return None
+    X = bf16_device_tensor(X, name)  # a host tensor is copied over as bfloat16
+    ldx = _ld(X, 0, X.shape[1])
+    if X.stride(1) != 1 or ldx % 8 or ldx < X.shape[1] or X.data_ptr() % 16:
+        return None
+    return X
+
+
+def _oja_steps_bf16(X: torch.Tensor, V: torch.Tensor, eta: float, b: int, nb: int, orth_every: int,
+                    xname: str) -> torch.Tensor:
+    """nb batches of b rows of the bfloat16 X (``_oja_bf16_samples``) through
+    deig_oja_steps_bf16: X with its own row stride, no copy, no ``oja_check``."""
+    d = X.shape[1]
+    k = _oja_basis(V, X, xname)
+    _call(X.device, "deig_oja_steps_bf16",
+          (X.data_ptr(), nb, b, d, _ld(X, 0, d), eta, V.data_ptr(), k, _ld(V, 1, d), int(orth_every)),
+          "deig_oja_workspace", (b, d, k))
+    return V
 
 
 def oja_check(device, b: int, d: int, k: int) -> None:
@@ -950,10 +983,28 @@ def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
     synchronise and raise ``DeigTimeoutError`` if a resident hand-off timed out (V is
     then NaN); ``check=False`` leaves the call asynchronous - then call ``oja_check``
     before any other op on this thread's stream (they share the workspace that holds
-    the timeout word).  Returns V."""
+    the timeout word).  Returns V.
+
+    bfloat16 samples are consumed as bfloat16 (include/deig.h deig_oja_steps_bf16: the
+    two-pass kernels with the sample as the MFMA operand, two products per fragment pair
+    instead of three, no float32 copy; the bits of ``algo="two_pass"`` on ``X.float()``)
+    when ``algo`` is "auto" or "two_pass" and X is a 2-D view with unit column stride,
+    d % 8 == 0, a row stride % 8 == 0 and a 16-byte aligned base - a row-strided view
+    such as ``x[:, :d]`` is read in place.  That route cannot time out: it makes no
+    ``oja_check`` call and stays asynchronous whatever ``check`` says.  Any other
+    bfloat16 input (``algo="resident"``, d % 8 == 4, odd strides) is widened to float32
+    first, as every bfloat16 input was before.  "auto" takes the bfloat16 kernels at every
+    shape, resident-eligible ones included: at config 4's shape (batch 4096, d = 3072,
+    k = 32, 64 batches, orth_every 8) they took 31.6 us per batch against 40.1 us for
+    widening plus the resident kernel and 50.0 us for widening plus the float32 two-pass
+    kernels, and at 4096 x 8192, k = 64, 84.8 against 140.1 us (profiles/oja_bf16.json,
+    tools/oja_bf16_bench.py)."""
+    b = int(batch)
+    x16 = _oja_bf16_samples(X, algo, "oja_steps")
+    if x16 is not None and 0 < b <= x16.shape[0]:
+        return _oja_steps_bf16(x16, V, eta, b, x16.shape[0] // b, orth_every, "X")
     X = _rowmajor_4(require_device_tensor(X, "oja_steps"), "X")
     n, d = X.shape
-    b = int(batch)
     nb = n // b if b > 0 else 0
     if nb < 1:
         raise ValueError(f"need at least one full batch of {batch} rows, got {n} rows")

@@ -66,7 +66,9 @@ class StreamingOja:
     the server's basis, columns in ascending-eigenvalue order
     (``aggregate="projector"``, the default) or, with ``aggregate="procrustes"``, the
     Procrustes-aligned average whose columns follow the server rank's basis before
-    the aggregation.
+    the aggregation.  bfloat16 batches are consumed as bfloat16 (``linalg.oja_steps``:
+    no float32 copy of a batch or a block; the bits of the same calls on
+    ``batch.float()``).
     """
 
     def __init__(self, V0: torch.Tensor, eta: float, agg_every: int = 64, server_rank: int = 0,

@@ -531,6 +531,29 @@ int deig_oja_steps_ex(const float* X, int64_t nb, int64_t b, int64_t d, int64_t 
  * clears the word). */
 int deig_oja_error(const void* ws, size_t ws_bytes, int64_t b, int64_t d, int k, void* stream);
 
+/* deig_oja_steps_f32 on bf16 samples taken as they are (no fp32 copy of X): the two-pass
+ * kernels with the sample as the MFMA A operand itself.  A bf16 value is its own hi piece
+ * and its lo piece is exactly zero, so each fp32 product takes two bf16 MFMAs (hi hi +
+ * hi lo) instead of three, over the same k-steps in the same order, and X is read at 2
+ * bytes an element.
+ * X: (nb*b) x d row-major bf16 (DEIG_BF16 elements), 16-byte aligned, d % 8 == 0, d >= 8,
+ * ldx % 8 == 0, ldx >= d; no element behind column d of a row is read.  V, k, ldv,
+ * orth_every as for deig_oja_steps_f32: 1 <= k <= min(64, d), any ldv >= d, element
+ * alignment of V, nothing behind row d of a V column touched.  A single step is nb = 1,
+ * orth_every = 1.
+ * Contract: the result has the bits of deig_oja_steps_ex(widened X, ..., DEIG_OJA_TWO_PASS,
+ * ...), widened = each element converted to fp32.  The resident kernel is never launched,
+ * whatever the shape.
+ * Workspace: deig_oja_workspace(b, d, k), the same layout; it may hold anything on entry.
+ * The call clears the workspace's timeout word and never sets it: deig_oja_error on that
+ * workspace returns DEIG_OK.  Asynchronous on `stream`: no allocation, no synchronisation, no
+ * atomics, no wait between workgroups; repeated calls give identical bits.  Argument errors
+ * are DEIG_EINVAL and a short or NULL workspace is DEIG_EWORKSPACE, both before any GPU work.
+ * Additive: probe for the symbol, deig_version() is unchanged. */
+int deig_oja_steps_bf16(const void* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
+                        float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* Projection onto an estimated eigenspace: Y = X W.
  * Replaces the notebook's  online_distributed_PCA = lambda X: X @ matrix_w
  * (Online Distributed PCA.ipynb raw line 345).  X: n x d row-major (ldx), W: d x k
