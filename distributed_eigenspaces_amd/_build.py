@@ -18,7 +18,7 @@ SOURCES = ["capi.hip", "solver.hip", "syrk.hip", "syrk_split.hip", "syrk_u8.hip"
 # Per-source extra flags.  sweep.hip: keep the split's scalar f32 subtractions
 # unpacked (v_pk_add_f32 beside MFMAs costs issue cycles, MI355X_MICROARCH.md).
 EXTRA_FLAGS = {"sweep.hip": ["-fno-slp-vectorize"], "syrk_split.hip": ["-fno-slp-vectorize"]}
-HEADERS = ["deig_internal.hpp", "skinny_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
+HEADERS = ["deig_internal.hpp", "skinny_tile.hpp", "syrk_image_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
 # Test-only variant (tests/test_gpu_oja_timeout.py): oja.hip with a zero spin bound, so
 # every resident hand-off times out and the DEIG_ETIMEOUT report can be exercised; the
 # other objects are the shipped library's.

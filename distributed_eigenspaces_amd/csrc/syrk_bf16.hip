@@ -11,18 +11,17 @@
 //    [k-step of 32 rows][g = 8-row group][feature, padded to 128][8 rows = 16 B], the 16
 //    bytes lane (g, feature) feeds to the MFMA.  Rows past n and features past d are zero;
 //    no element behind column d of a row is read.
-//  * bf16_syrk_kernel: one workgroup per (lower 128 x 128 tile, K segment), 4 waves with
-//    64 x 64 wave tiles (4 x 4 MFMA blocks), LDS double buffer of 64-row stages (two MFMA
-//    K-steps per barrier) fed from a register ring of 16-byte loads, ds_read_b128 operand
-//    reads, fp32 accumulators.  Each item stores its accumulators to a slab of its own
-//    (fragment order: one 16-byte store per lane and MFMA block, fully coalesced).  Plain
-//    independent workgroups: nobody waits on anybody, no atomics.
+//  * bf16_syrk_kernel: one workgroup per (lower 128 x 128 tile, K segment) runs the tile K
+//    loop of syrk_image_tile.hpp with 64-row stages (two MFMA K-steps per barrier) and fp32
+//    accumulators, and stores them to a slab of its own (fragment order: one 16-byte store per
+//    lane and MFMA block, fully coalesced).  Plain independent workgroups: nobody waits on
+//    anybody, no atomics.
 //  * bf16_reduce_kernel: one workgroup per tile adds the segments' slabs in order, applies
 //    alpha, adds S when accumulating (the caller's flag, and every chunk after the first),
 //    and writes S[i][j] and, through LDS, the mirror S[j][i] from the same value.
 // Every slab entry that is read was written by this call (a diagonal tile's upper wave
 // block is neither), so the workspace may hold anything on entry.
-#include "bf16_split.hpp"
+#include "syrk_image_tile.hpp"
 
 namespace deig {
 namespace {
@@ -42,21 +41,22 @@ constexpr int KB = 32;              // rows per MFMA K-step
 #endif
 constexpr int SB = DEIG_AB_BF16_STAGE_ROWS;  // rows per LDS stage (a multiple of KB)
 constexpr int KS = SB / 32;                  // K-steps per stage
-constexpr int NH = 2 * KS;                   // 16-byte pieces per thread, panel and stage
-constexpr int PF = DEIG_AB_BF16_PF;          // stages in the register ring (even)
 constexpr int WGS = DEIG_AB_BF16_WGS;        // workgroups per CU the kernel is built for
-constexpr int TB = 128;             // output tile edge (features)
-constexpr int THR = 256;            // 4 waves, 2 x 2 wave tiles of 64 x 64
+using namespace itile;  // TB, THR, img_off, tile_of, frag_row, frag_col
+// The shared K loop's operation; stage st is the K-steps kb = KS st .. KS st + KS - 1.
+struct Bf16Op {
+  static constexpr int KS = SB / 32, PF = DEIG_AB_BF16_PF;  // PF: stages in the register ring (even)
+  typedef bf16x8 Frag;
+  typedef f32x4 Acc;
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
 constexpr int kFlushRows = 16384;   // rows per K segment at most (syrk_split.hip flush_ktiles)
 constexpr int kSegStages = kFlushRows / SB;
 constexpr int kMinSegs = 4, kMaxSegs = 32;
 constexpr int kItemsTarget = 512;   // two workgroups on each of 256 CUs
 constexpr int64_t kTileFloats = (int64_t)TB * TB;
-
-// Image: [kb][g][feature][8 rows]; stage st is the K-steps kb = KS st .. KS st + KS - 1.
-__host__ __device__ inline int64_t img_off(int64_t kb, int g, int64_t f, int64_t fpad) {
-  return ((kb * 4 + g) * fpad + f) * 16;
-}
 
 // grid (cdiv(fpad, 512), YB): wave g of a block owns the 8-row group g of K-steps kb =
 // by, by + YB, ..., lane l the features 512 bx + 8 l .. + 7: eight 16-byte row loads (1 KiB
@@ -92,15 +92,6 @@ __global__ __launch_bounds__(THR) void bf16_prep_kernel(const uint16_t* __restri
   }
 }
 
-// Lower tile t (row-major over the triangle) -> (ti, tj), tj <= ti.
-__device__ __forceinline__ void tile_of(int t, int& ti, int& tj) {
-  int i = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-  while (i * (i + 1) / 2 > t) --i;
-  while ((i + 1) * (i + 2) / 2 <= t) ++i;
-  ti = i;
-  tj = t - i * (i + 1) / 2;
-}
-
 struct Bf16Sched {
   const uint8_t* img;
   float* slabs;  // [seg][tile][wave][MFMA block a, b][lane][4]
@@ -108,109 +99,35 @@ struct Bf16Sched {
   int T, nseg;
 };
 
-// One item = (lower tile, K segment).  LDS: 2 stages x (A panel, B panel), a panel = 4 KS row
-// groups x 128 features x 16 B (16 KiB at SB = 64), the same bytes as the image's runs.  Wave (wi, wj)
-// owns rows 64 wi.. and columns 64 wj.. of the tile; lane l reads the fragment of feature
-// 16 a + (l & 15), row group l >> 4 of a K-step: within a ds_read_b128 lane group the 16
-// addresses cover 64 distinct banks.
+// One item = (lower tile, K segment); the tile, its LDS stages and the K loop are
+// syrk_image_tile.hpp's.
 __global__ __launch_bounds__(THR, WGS) void bf16_syrk_kernel(Bf16Sched s) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[2][2][KS * 4 * TB * 16];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[itile::lds_bytes<Bf16Op>()];
   const int item = blockIdx.x;
   const int tile = item % s.T, seg = item / s.T;
   int ti, tj;
   tile_of(tile, ti, tj);
-  const bool diag = ti == tj;
-  const bool active = !(diag && wi < wj);  // the upper block of a diagonal tile is a mirror
+  const itile::Item it = itile::item_of(ti, tj);
   const int64_t k0 = s.nst * seg / s.nseg, k1 = s.nst * (seg + 1) / s.nseg;
-  const int64_t i0 = (int64_t)ti * TB, j0 = (int64_t)tj * TB;
   if (k0 >= k1) return;  // (never: nseg <= nst; whole block)
-
-  // staging: thread t moves the 16-byte pieces c = t + 256 h of each panel (4 KS row groups
-  // x 128 features)
-  auto load = [&](int64_t st, u32x4 (&ra)[NH], u32x4 (&rb)[NH]) {
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-      const int c = tid + h * THR;
-      const int grp = c >> 7, fl = c & 127;
-      // (unconditional: a diagonal tile loads its panel twice - a branch around the B loads
-      // would make the compiler's counted waits conservative)
-      ra[h] = *reinterpret_cast<const u32x4*>(s.img + img_off(KS * st + (grp >> 2), grp & 3, i0 + fl, s.fpad));
-      rb[h] = *reinterpret_cast<const u32x4*>(s.img + img_off(KS * st + (grp >> 2), grp & 3, j0 + fl, s.fpad));
-    }
-  };
-  auto put = [&](int b, const u32x4 (&ra)[NH], const u32x4 (&rb)[NH]) {
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-      const int c = tid + h * THR;
-      *reinterpret_cast<u32x4*>(&lds[b][0][c * 16]) = ra[h];
-      *reinterpret_cast<u32x4*>(&lds[b][1][c * 16]) = rb[h];
-    }
-  };
-
   f32x4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // K loop: LDS double buffer fed from a PF-deep register ring - the loads of stage kk + PF
-  // are issued while kk's MFMAs run.  Loads are unpredicated (clamped to the last stage) so
-  // that the compiler's counted waits keep the ring in flight; PF even: buffer = u & 1.
-  u32x4 ra[PF][NH], rb[PF][NH];
-  auto clampk = [&](int64_t st) { return st < k1 ? st : k1 - 1; };
-#pragma unroll
-  for (int u = 0; u < PF; ++u) load(clampk(k0 + u), ra[u], rb[u]);
-  put(0, ra[0], rb[0]);
-  __syncthreads();
-  const int g = lane >> 4, c = lane & 15;
-  auto body = [&](int64_t kk, int u) {
-    load(clampk(kk + PF), ra[u], rb[u]);  // slot u's stage is already in LDS
-    const int b = u & 1;
-    if (active) {
-      const uint8_t* pa = &lds[b][0][0];
-      const uint8_t* pb = diag ? pa : &lds[b][1][0];
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        bf16x8 fa[4], fb[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          fa[a] = *reinterpret_cast<const bf16x8*>(pa + ((ks * 4 + g) * TB + 64 * wi + 16 * a + c) * 16);
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb)
-          fb[bb] = *reinterpret_cast<const bf16x8*>(pb + ((ks * 4 + g) * TB + 64 * wj + 16 * bb + c) * 16);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int bb = 0; bb < 4; ++bb)
-            acc[a][bb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[bb], acc[a][bb], 0, 0, 0);
-      }
-    }
-    put(b ^ 1, ra[(u + 1) % PF], rb[(u + 1) % PF]);  // stage kk + 1 (a clamped copy past k1)
-    __syncthreads();
-  };
-  int64_t kk = k0;
-  for (; kk + PF <= k1; kk += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) body(kk + u, u);
-  }
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (kk + u < k1) body(kk + u, u);
-  if (!active) return;
+  itile::k_loop<Bf16Op>(s.img, s.fpad, it, k0, k1, lds, acc);
+  if (!it.active) return;
   // the slab of this item, in fragment order: block (a, b) of the wave is 64 lanes x 16 B
   f32x4* slab = reinterpret_cast<f32x4*>(s.slabs + ((int64_t)seg * s.T + tile) * kTileFloats) +
-                wave * 16 * 64 + lane;
+                it.wave * 16 * 64 + it.lane;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) slab[(a * 4 + b) * 64] = acc[a][b];
 }
 
-// One workgroup per lower tile, one 64-row half of it at a time.  C/D map of the MFMA:
-// lane l, register r of block (a, b) of wave (wi, wj) is row 64 wi + 16 a + 4 (l >> 4) + r,
-// column 64 wj + 16 b + (l & 15) of the tile.  v = alpha (sum of the segments in order)
+// One workgroup per lower tile, one 64-row half of it at a time; slab entries are placed by
+// the C/D map (frag_row, frag_col).  v = alpha (sum of the segments in order)
 // (+ S[i][j], the lower entry, when accumulating) goes to LDS (row stride 129: both the row
 // and the column walk are conflict-free), then to S[i][j] in rows of 128 contiguous floats
 // and to S[j][i] in runs of 64: both triangles hold the same bits.
@@ -235,10 +152,10 @@ __global__ __launch_bounds__(THR) void bf16_reduce_kernel(const float* __restric
       f32x4 v = *reinterpret_cast<const f32x4*>(p);
       for (int sg = 1; sg < nseg; ++sg)
         v += *reinterpret_cast<const f32x4*>(p + (int64_t)sg * T * kTileFloats);
-      const int jl = 64 * wj + 16 * (ab & 3) + (lane & 15);
+      const int jl = frag_col(wj, ab & 3, lane);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int il = 16 * (ab >> 2) + 4 * (lane >> 4) + r;
+        const int il = frag_row(0, ab >> 2, lane, r);  // (within the half: wi = h is in i0)
         const int64_t i = i0 + il, j = j0 + jl;
         float x = alpha * v[r];
         if (beta && i < d && j < d && j <= i) x += S[i * lds + j];

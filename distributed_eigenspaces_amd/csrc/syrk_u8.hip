@@ -24,28 +24,56 @@
 // buffer, int32 MFMA accumulators, int64 atomic adds: exact and order independent,
 // hence deterministic), u8_finalize_kernel (combine planes + corrections in int64,
 // one double rounding, both triangles from the same value: bit-exact symmetry).
-#include "deig_internal.hpp"
+#include <type_traits>
+
+#include "syrk_image_tile.hpp"
 
 namespace deig {
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
+using namespace itile;  // TB, THR, img_off, tile_of, frag_row, frag_col
 constexpr int KB = 64;        // rows per K-step (one MFMA 16x16x64 depth)
-constexpr int TB = 128;       // output tile edge (features)
 constexpr int FPAD = 128;     // features padded to a multiple of this
-constexpr int SYRK_THR = 256;  // 4 waves, 2 x 2 wave tiles of 64 x 64
+constexpr int SYRK_THR = THR;
 constexpr int PREP_THR = 256;  // prep: 4 waves (one 16-row group each), 4 features per lane
 constexpr int MAX_SEG_KB = 1024;  // <= 65536 rows per item: int32 accumulators cannot overflow
 constexpr int PREP_YB = 128;
 
 inline int u8_planes(int mode) { return mode == DEIG_U8_GRAY3 ? 3 : 1; }
 
-// Image: plane-major, then [kb][g = 16-row group][feature][16 bytes = rows 16g..16g+15].
-__host__ __device__ inline int64_t img_off(int64_t plane, int64_t kb, int g, int64_t f, int64_t nkb,
-                                           int64_t fpad) {
-  return (((plane * nkb + kb) * 4 + g) * fpad + f) * 16;
+// The shared K loop's operation: one K-step of 64 rows per LDS stage.
+struct U8Op {
+  static constexpr int KS = 1, PF = 4;
+  typedef i32x4 Frag;
+  typedef i32x4 Acc;
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+  }
+};
+
+// Image: plane-major, then itile's [kb][g = 16-row group][feature][16 bytes = rows 16g..16g+15].
+__host__ __device__ inline int64_t plane_off(int64_t plane, int64_t nkb, int64_t fpad) {
+  return plane * nkb * 4 * fpad * 16;
+}
+
+// r + g + b of pixel u (0..3) of the 12 interleaved bytes in b[0..2].
+__device__ __forceinline__ uint32_t gray_sum(const uint32_t (&b)[3], int u) {
+  uint32_t s = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int byte = 3 * u + c;
+    s += (b[byte >> 2] >> (8 * (byte & 3))) & 0xffu;
+  }
+  return s;
+}
+
+// mode -> f(std::integral_constant<int, MODE>): the kernels take the mode as a template argument.
+template <class F>
+void with_mode(int mode, F&& f) {
+  if (mode == DEIG_U8_RAW)
+    f(std::integral_constant<int, DEIG_U8_RAW>{});
+  else
+    f(std::integral_constant<int, DEIG_U8_GRAY3>{});
 }
 
 // 4 x 4 byte transpose: r[q] holds byte u = feature u of row q; out[u] holds byte q =
@@ -81,10 +109,9 @@ __global__ __launch_bounds__(PREP_THR) void u8_prep_kernel(const uint8_t* __rest
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   if (blockIdx.x == 0 && blockIdx.y == 0) {  // the tile order: lower triangle, row-major
     for (int i = threadIdx.x; i < nt * (nt + 1) / 2; i += PREP_THR) {
-      int ti = (int)((sqrtf(8.f * (float)i + 1.f) - 1.f) * 0.5f);
-      while (ti * (ti + 1) / 2 > i) --ti;
-      while ((ti + 1) * (ti + 2) / 2 <= i) ++ti;
-      order[i] = ti | ((i - ti * (ti + 1) / 2) << 16);
+      int ti, tj;
+      tile_of(i, ti, tj);
+      order[i] = ti | (tj << 16);
     }
   }
   const int f = blockIdx.x * 256 + lane * 4;
@@ -114,13 +141,8 @@ __global__ __launch_bounds__(PREP_THR) void u8_prep_kernel(const uint8_t* __rest
           uint32_t ph = 0, pl = 0, pw = 0;
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            int s = 0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-              const int byte = 3 * u + c;
-              s += (int)((b[byte >> 2] >> (8 * (byte & 3))) & 0xffu);
-            }
-            const int t = ok ? s - 384 : 0;  // padding rows contribute nothing
+            const int s = (int)gray_sum(b, u);  // (outside the select: inside it, it becomes a branch)
+            const int t = ok ? s - 384 : 0;     // padding rows contribute nothing
             const int h = t >> 4, l = t & 15, w = h + l;
             csum[u] += t;
             ph |= ((uint32_t)h & 0xffu) << (8 * u);
@@ -145,7 +167,7 @@ __global__ __launch_bounds__(PREP_THR) void u8_prep_kernel(const uint8_t* __rest
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          *reinterpret_cast<u32x4*>(img + img_off(pl, kb, g, f + u, nkb, fpad)) =
+          *reinterpret_cast<u32x4*>(img + plane_off(pl, nkb, fpad) + img_off(kb, g, f + u, fpad)) =
               u32x4{col[u][0], col[u][1], col[u][2], col[u][3]};
       }
     }
@@ -265,15 +287,7 @@ __global__ __launch_bounds__(256) void u8_colsum_kernel(const uint8_t* __restric
         const uint32_t* p = reinterpret_cast<const uint32_t*>(X + row * ldx + 3 * f);
         const uint32_t b[3] = {p[0], p[1], p[2]};
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          uint32_t t = 0;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const int byte = 3 * u + c;
-            t += (b[byte >> 2] >> (8 * (byte & 3))) & 0xffu;
-          }
-          sum[u] += t;
-        }
+        for (int u = 0; u < 4; ++u) sum[u] += gray_sum(b, u);
       }
     }
   }
@@ -296,11 +310,8 @@ __global__ __launch_bounds__(256) void u8_colsum_finish_kernel(const unsigned lo
   sums[j] = MODE == DEIG_U8_GRAY3 ? v / 3.0 : v;
 }
 
-// One item = (plane, lower tile, K segment).  LDS: 2 stages x (A panel, B panel),
-// each panel = 4 row groups x 128 features x 16 B = 8 KiB, the same bytes as the
-// image's [kb][g][f0 .. f0+127] runs.  Wave (wi, wj) owns rows 64 wi.. and columns
-// 64 wj.. of the tile: 4 x 4 MFMA blocks, lane l reads the A fragment of feature
-// 16 a + (l & 15), row group l >> 4 (16 consecutive rows = 16 bytes).
+// One item = (plane, lower tile, K segment); the tile, its LDS stages (32 KiB), the K loop
+// and the C/D map (frag_row, frag_col) are syrk_image_tile.hpp's.
 // DIRECT (raw mode, the whole K range in one item: n <= 65536 rows, so the int32
 // accumulators are the exact sums): the epilogue adds the mean terms in int64,
 // scales once in double (as u8_finalize_kernel) and stores S[i][j] and S[j][i] -
@@ -310,40 +321,14 @@ __global__ __launch_bounds__(256) void u8_colsum_finish_kernel(const unsigned lo
 // is u8_centered_value of the same accumulators and column sums; the K loop is the same code.
 template <bool DIRECT, bool CENTERED = false>
 __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[2][2][4 * TB * 16];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[itile::lds_bytes<U8Op>()];
   const int item = blockIdx.x;
   const int plane = blockIdx.y;
   const int tile = item % s.T, seg = item / s.T;
   const int tt = s.order[tile];
-  const int ti = tt & 0xffff, tj = tt >> 16;
-  const bool diag = ti == tj;
-  const bool active = !(diag && wi < wj);  // the upper block of a diagonal tile is a mirror
+  const itile::Item it = itile::item_of(tt & 0xffff, tt >> 16);
+  const auto& [tid, lane, wave, wi, wj, diag, active, i0, j0] = it;  // (for the epilogues)
   const int64_t k0 = s.nkb * seg / s.nseg, k1 = s.nkb * (seg + 1) / s.nseg;
-  const int64_t i0 = (int64_t)ti * TB, j0 = (int64_t)tj * TB;
-
-  // staging: thread t moves 16 B chunks c = t and t + 256 of each panel (512 chunks
-  // = 4 groups x 128 features)
-  auto load = [&](int64_t kb, u32x4 (&ra)[2], u32x4 (&rb)[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = tid + h * SYRK_THR;
-      const int g = c >> 7, fl = c & 127;
-      // (unconditional: a diagonal tile loads its panel twice - a branch around the B
-      // loads would make the compiler's counted waits conservative)
-      ra[h] = *reinterpret_cast<const u32x4*>(s.img + img_off(plane, kb, g, i0 + fl, s.nkb, s.fpad));
-      rb[h] = *reinterpret_cast<const u32x4*>(s.img + img_off(plane, kb, g, j0 + fl, s.nkb, s.fpad));
-    }
-  };
-  auto put = [&](int st, const u32x4 (&ra)[2], const u32x4 (&rb)[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = tid + h * SYRK_THR;
-      *reinterpret_cast<u32x4*>(&lds[st][0][c * 16]) = ra[h];
-      *reinterpret_cast<u32x4*>(&lds[st][1][c * 16]) = rb[h];
-    }
-  };
 
   i32x4 acc[4][4];
 #pragma unroll
@@ -352,72 +337,29 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
     for (int b = 0; b < 4; ++b) acc[a][b] = i32x4{0, 0, 0, 0};
 
   if (k0 >= k1) return;  // (whole block: an empty K segment adds nothing)
-  // K loop: LDS double buffer fed from a PF-deep register ring - the loads of k-step
-  // kk + PF are issued while kk's MFMAs run, so each load has PF - 1 steps to land
-  // (one step ahead, a c1 worker shard took 149 us: every step waited out a global
-  // load latency).  Loads are unpredicated (clamped to the last k-step) so that the
-  // compiler's counted waits keep the ring in flight; PF even: stage = u & 1.
-  constexpr int PF = 4;
-  u32x4 ra[PF][2], rb[PF][2];
-  auto clampk = [&](int64_t kb) { return kb < k1 ? kb : k1 - 1; };
-#pragma unroll
-  for (int u = 0; u < PF; ++u) load(clampk(k0 + u), ra[u], rb[u]);
-  put(0, ra[0], rb[0]);
-  __syncthreads();
-  const int g = lane >> 4, c = lane & 15;
-  auto body = [&](int64_t kk, int u) {
-    load(clampk(kk + PF), ra[u], rb[u]);  // slot u's k-step is already in LDS
-    const int st = u & 1;
-    if (active) {
-      const uint8_t* pa = &lds[st][0][0];
-      const uint8_t* pb = diag ? pa : &lds[st][1][0];
-      i32x4 fa[4], fb[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-        fa[a] = *reinterpret_cast<const i32x4*>(pa + (g * TB + 64 * wi + 16 * a + c) * 16);
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        fb[b] = *reinterpret_cast<const i32x4*>(pb + (g * TB + 64 * wj + 16 * b + c) * 16);
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[a], fb[b], acc[a][b], 0, 0, 0);
-    }
-    put(st ^ 1, ra[(u + 1) % PF], rb[(u + 1) % PF]);  // k-step kk + 1 (a clamped copy past k1)
-    __syncthreads();
-  };
-  int64_t kb = k0;
-  for (; kb + PF <= k1; kb += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) body(kb + u, u);
-  }
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (kb + u < k1) body(kb + u, u);
+  itile::k_loop<U8Op>(s.img + plane_off(plane, s.nkb, s.fpad), s.fpad, it, k0, k1, lds, acc);
   if (!DIRECT && !active) return;  // (the direct epilogue has barriers: every wave stays)
-  // C/D map (gfx950, dtype independent): column = lane & 15, row = 4 (lane >> 4) + reg
   if constexpr (DIRECT) {
     // every column sum loaded up front at clamped indices (a load inside the i < d
     // branch waited out its latency alone: 16 serialised loads per wave)
     long long cjv[4], civ[4][4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
+      const int64_t j = j0 + frag_col(wj, b, lane);
       cjv[b] = (long long)s.colsum[j < s.d ? j : s.d - 1];
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t i = i0 + 64 * wi + 16 * a + 4 * (lane >> 4) + r;
+        const int64_t i = i0 + frag_row(wi, a, lane, r);
         civ[a][r] = (long long)s.colsum[i < s.d ? i : s.d - 1];
       }
     double ejv[4] = {0.0, 0.0, 0.0, 0.0};
     if constexpr (CENTERED) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
+        const int64_t j = j0 + frag_col(wj, b, lane);
         ejv[b] = s.e[j < s.d ? j : s.d - 1];
       }
     }
@@ -427,12 +369,12 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t i = i0 + 64 * wi + 16 * a + 4 * (lane >> 4) + r;
+        const int64_t i = i0 + frag_row(wi, a, lane, r);
         double ei = 0.0;
         if constexpr (CENTERED) ei = s.e[i < s.d ? i : s.d - 1];
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-          const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
+          const int64_t j = j0 + frag_col(wj, b, lane);
           double v;
           if constexpr (CENTERED) {
             v = u8_centered_value<DEIG_U8_RAW>((long long)acc[a][b][r], civ[a][r], cjv[b], ei,
@@ -456,10 +398,10 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
         for (int a = 0; a < 4; ++a)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int64_t i = i0 + 64 * wi + 16 * a + 4 * (lane >> 4) + r;
+            const int64_t i = i0 + frag_row(wi, a, lane, r);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-              const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
+              const int64_t j = j0 + frag_col(wj, b, lane);
               if (i < s.d && j < s.d && !(diag && j > i)) s.S[i * s.lds + j] = vf[a][b][r];
             }
           }
@@ -470,7 +412,7 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
       // accumulators, every mirror instruction scattered 4-byte writes over 64 rows:
       // r04 A/B in one process on the c1 worker shard, 99.7 vs 102.5 us per covariance,
       // bit-identical, profiles/r04b_u8_mirror_ab.log.)
-      float* T = reinterpret_cast<float*>(&lds[0][0][0]);
+      float* T = reinterpret_cast<float*>(lds);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         if (active && wi == h)
@@ -478,10 +420,10 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
           for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int il = 16 * a + 4 * (lane >> 4) + r;
+              const int il = frag_row(0, a, lane, r);  // (within the half)
 #pragma unroll
               for (int b = 0; b < 4; ++b) {
-                const int jl = 64 * wj + 16 * b + (lane & 15);
+                const int jl = frag_col(wj, b, lane);
                 T[il * 128 + (jl ^ (il & 31))] = vf[a][b][r];
               }
             }
@@ -518,8 +460,8 @@ __global__ __launch_bounds__(SYRK_THR, 2) void u8_syrk_kernel(U8Sched s) {
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t i = i0 + 64 * wi + 16 * a + 4 * (lane >> 4) + r;
-        const int64_t j = j0 + 64 * wj + 16 * b + (lane & 15);
+        const int64_t i = i0 + frag_row(wi, a, lane, r);
+        const int64_t j = j0 + frag_col(wj, b, lane);
         if (diag && j > i) continue;
         atomicAdd(Gp + i * s.fpad + j, (unsigned long long)(long long)acc[a][b][r]);
       }
@@ -603,18 +545,11 @@ size_t u8_centered_off_e(const U8Layout& L) { return align_up(L.total, 256); }
 int u8_run(const char* what, bool centered, const uint8_t* X, int64_t n, int64_t d, int64_t ldx,
            int mode, const double* center, double alpha, float* S, int64_t lds, double* S64,
            int64_t lds64, double* mean_out, void* ws, size_t ws_bytes, hipStream_t stream) {
-  DEIG_REQUIRE(mode == DEIG_U8_RAW || mode == DEIG_U8_GRAY3, "%s: unknown mode %d", what, mode);
-  DEIG_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
-  DEIG_REQUIRE(d >= 4 && d % 4 == 0 && d <= (1 << 15),
-               "%s: d must be a multiple of 4 in [4, 32768] (got %lld)", what, (long long)d);
-  const int64_t need = mode == DEIG_U8_RAW ? d : 3 * d;
-  DEIG_REQUIRE(ldx >= need && ldx % 4 == 0, "%s: ldx must be >= %lld bytes and a multiple of 4", what,
-               (long long)need);
+  if (int rc = u8_check_shape(what, n, d, ldx, mode, 1 << 15)) return rc;
   DEIG_REQUIRE(S || S64, "%s: need S and/or S64", what);
   DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) & 3u) == 0, "%s: X must be 4-byte aligned", what);
   DEIG_REQUIRE(!S || lds >= d, "%s: lds must be >= d", what);
   DEIG_REQUIRE(!S64 || lds64 >= d, "%s: lds64 must be >= d", what);
-  DEIG_REQUIRE(n <= (int64_t(1) << 40), "%s: n too large", what);
   DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % 8 == 0 &&
                    reinterpret_cast<uintptr_t>(mean_out) % 8 == 0,
                "%s: center and mean_out must be 8-byte aligned", what);
@@ -638,21 +573,16 @@ int u8_run(const char* what, bool centered, const uint8_t* X, int64_t n, int64_t
     DEIG_HIP_CHECK(hipMemsetAsync(G, 0, sizeof(unsigned long long) * L.planes * L.fpad * L.fpad, stream));
   const int yb = (int)(L.nkb < PREP_YB ? L.nkb : PREP_YB);
   const dim3 pg((unsigned)(L.fpad / 256 + (L.fpad % 256 ? 1 : 0)), (unsigned)yb);
-  if (mode == DEIG_U8_RAW)
-    hipLaunchKernelGGL(u8_prep_kernel<DEIG_U8_RAW>, pg, dim3(PREP_THR), 0, stream, X, n, ldx,
-                       (int)d, L.fpad, L.nkb, img, col, (int)L.nt, order);
-  else
-    hipLaunchKernelGGL(u8_prep_kernel<DEIG_U8_GRAY3>, pg, dim3(PREP_THR), 0, stream, X, n, ldx,
-                       (int)d, L.fpad, L.nkb, img, col, (int)L.nt, order);
+  with_mode(mode, [&](auto m) {
+    hipLaunchKernelGGL(u8_prep_kernel<m()>, pg, dim3(PREP_THR), 0, stream, X, n, ldx, (int)d, L.fpad,
+                       L.nkb, img, col, (int)L.nt, order);
+  });
   DEIG_HIP_CHECK(hipGetLastError());
   if (centered) {  // the centre terms (and the own mean) from the column sums
-    const dim3 cg((unsigned)cdiv(L.fpad, 256));
-    if (mode == DEIG_U8_RAW)
-      hipLaunchKernelGGL(u8_center_kernel<DEIG_U8_RAW>, cg, dim3(256), 0, stream, col, center, d,
-                         L.fpad, n, e, mean_out);
-    else
-      hipLaunchKernelGGL(u8_center_kernel<DEIG_U8_GRAY3>, cg, dim3(256), 0, stream, col, center, d,
-                         L.fpad, n, e, mean_out);
+    with_mode(mode, [&](auto m) {
+      hipLaunchKernelGGL(u8_center_kernel<m()>, dim3((unsigned)cdiv(L.fpad, 256)), dim3(256), 0, stream,
+                         col, center, d, L.fpad, n, e, mean_out);
+    });
     DEIG_HIP_CHECK(hipGetLastError());
   }
   // K segments: enough items to fill the chip twice over, each <= MAX_SEG_KB row
@@ -694,21 +624,10 @@ int u8_run(const char* what, bool centered, const uint8_t* X, int64_t n, int64_t
                      dim3(SYRK_THR), 0, stream, s);
   DEIG_HIP_CHECK(hipGetLastError());
   const dim3 fg((unsigned)cdiv(d * d, 256));
-  if (mode == DEIG_U8_RAW) {
-    if (centered)
-      hipLaunchKernelGGL((u8_finalize_kernel<DEIG_U8_RAW, true>), fg, dim3(256), 0, stream, G, col,
-                         L.fpad, d, n, alpha, div, S, lds, S64, lds64, e);
-    else
-      hipLaunchKernelGGL(u8_finalize_kernel<DEIG_U8_RAW>, fg, dim3(256), 0, stream, G, col, L.fpad,
-                         d, n, alpha, div, S, lds, S64, lds64, e);
-  } else {
-    if (centered)
-      hipLaunchKernelGGL((u8_finalize_kernel<DEIG_U8_GRAY3, true>), fg, dim3(256), 0, stream, G, col,
-                         L.fpad, d, n, alpha, div, S, lds, S64, lds64, e);
-    else
-      hipLaunchKernelGGL(u8_finalize_kernel<DEIG_U8_GRAY3>, fg, dim3(256), 0, stream, G, col, L.fpad,
-                         d, n, alpha, div, S, lds, S64, lds64, e);
-  }
+  with_mode(mode, [&](auto m) {
+    auto k = centered ? u8_finalize_kernel<m(), true> : u8_finalize_kernel<m(), false>;
+    hipLaunchKernelGGL(k, fg, dim3(256), 0, stream, G, col, L.fpad, d, n, alpha, div, S, lds, S64, lds64, e);
+  });
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
 }
@@ -774,13 +693,10 @@ int colsum_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mo
   const int64_t yb = cdiv(n, 4) < 128 ? cdiv(n, 4) : 128;
   const dim3 grid((unsigned)cdiv(d, 256), (unsigned)yb);
   const dim3 fg((unsigned)cdiv(d, 256));
-  if (mode == DEIG_U8_RAW) {
-    hipLaunchKernelGGL(u8_colsum_kernel<DEIG_U8_RAW>, grid, dim3(256), 0, stream, X, n, ldx, d, acc);
-    hipLaunchKernelGGL(u8_colsum_finish_kernel<DEIG_U8_RAW>, fg, dim3(256), 0, stream, acc, d, sums);
-  } else {
-    hipLaunchKernelGGL(u8_colsum_kernel<DEIG_U8_GRAY3>, grid, dim3(256), 0, stream, X, n, ldx, d, acc);
-    hipLaunchKernelGGL(u8_colsum_finish_kernel<DEIG_U8_GRAY3>, fg, dim3(256), 0, stream, acc, d, sums);
-  }
+  with_mode(mode, [&](auto m) {
+    hipLaunchKernelGGL(u8_colsum_kernel<m()>, grid, dim3(256), 0, stream, X, n, ldx, d, acc);
+    hipLaunchKernelGGL(u8_colsum_finish_kernel<m()>, fg, dim3(256), 0, stream, acc, d, sums);
+  });
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
 }

@@ -9,6 +9,7 @@ in-tree distributed_eigenspaces_amd/libdeig.so.
 
   python tools/ab.py build "MACRO=V [-DOTHER=W]" tools/ab_libs/libdeig_x.so   # here (CPU)
   python tools/ab.py syrk  REPS N D LIB [LIB ...]          # split3 covariance, ms per op
+  python tools/ab.py cov   KIND REPS N D LIB [LIB ...]     # KIND u8raw | u8gray | bf16, us per op
   python tools/ab.py sweep REPS D P MODE LIB [LIB ...]     # solver sweep chain, us per sweep
                                                            # MODE half | bf16x3 | bf16x5 | bf16x6
   python tools/ab.py oja   REPS ORTH LIB [LIB ...]         # config-4 Oja, us per batch
@@ -129,6 +130,59 @@ def ab_syrk(reps, n, d, paths):
     report(times, lambda p: torch.equal(outs[p], ref), "ms",
            lambda p, med: f" = {flop / med / 1e9 / 2.5e3:.4f} of bf16 peak, max|S - S_f64| / max|S| on 64 "
                           f"columns {((outs[p][:, cols].double() - S64).abs().max().item()) / scale:.2e}")
+
+
+# ---------------------------------------------------------------- cov (uint8, bf16 samples)
+def ab_cov(kind, reps, n, d, paths):
+    """Covariance of uint8 (u8raw | u8gray: deig_syrk_u8, fp32 S, alpha = 1 / n) or bf16 samples
+    (deig_syrk_bf16).  A refactor's check lists the parent build twice (two file copies A, A')
+    and then the new build: the gap between the two parent medians is what the run cannot
+    resolve, and the JSON line says whether each later build is within it."""
+    import json
+    import torch
+    from distributed_eigenspaces_amd import _lib, synthetic
+    libs = load_libs(paths)
+    dev = torch.device("cuda", 0)
+    U = synthetic.planted_basis(d, 64 if d >= 64 else d, 0, dev)
+    if kind == "bf16":
+        X = synthetic.spiked_samples(n, U, seed=1).to(torch.bfloat16)
+        nbytes = max(L.deig_syrk_bf16_workspace(n, d) for _, L in libs)
+    else:
+        mode = _lib.U8_MODES[kind[2:]]
+        X = synthetic.spiked_bytes(n, U, seed=1, channels=3 if kind == "u8gray" else 0).view(n, -1)
+        nbytes = max(L.deig_syrk_u8_workspace(n, d, mode) for _, L in libs)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    S = {p: torch.empty(d, d, device=dev) for p, _ in libs}
+    st = torch.cuda.current_stream(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    inner = 20 if n * d * d < 1e12 else 1  # short shapes: time a run of calls
+
+    def run(path, L):
+        torch.cuda.synchronize()
+        e0.record(st)
+        for _ in range(inner):
+            if kind == "bf16":
+                rc = L.deig_syrk_bf16(X.data_ptr(), n, d, X.stride(0), ctypes.c_float(1.0 / n),
+                                      S[path].data_ptr(), d, 0, ws.data_ptr(), nbytes, st.cuda_stream)
+            else:
+                rc = L.deig_syrk_u8(X.data_ptr(), n, d, X.stride(0), mode, 1.0 / n, S[path].data_ptr(), d,
+                                    None, d, ws.data_ptr(), nbytes, st.cuda_stream)
+            assert rc == 0, L.deig_last_error()
+        e1.record(st)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / inner * 1e3, S[path]
+
+    times, outs = interleave(libs, reps, run)
+    ref = outs[libs[0][0]]
+    report(times, lambda p: torch.equal(outs[p], ref), f"us ({kind} {n} x {d})")
+    med = {p: statistics.median(ts) for p, ts in times.items()}
+    res = {"kind": kind, "n": n, "d": d, "reps": reps, "median_us": {p: round(m, 2) for p, m in med.items()},
+           "bit_identical_to_first": {p: bool(torch.equal(outs[p], ref)) for p in med}}
+    if len(paths) >= 3:
+        a, a2 = med[paths[0]], med[paths[1]]
+        res["gap_us"] = round(abs(a - a2), 2)
+        res["within_gap"] = {p: bool(med[p] <= max(a, a2) + abs(a - a2)) for p in paths[2:]}
+    print("JSON " + json.dumps(res), flush=True)
 
 
 # ---------------------------------------------------------------- sweep
@@ -305,6 +359,8 @@ def main(argv):
         build(a[0], a[1])
     elif cmd == "syrk":
         ab_syrk(int(a[0]), int(a[1]), int(a[2]), a[3:])
+    elif cmd == "cov":
+        ab_cov(a[0], int(a[1]), int(a[2]), int(a[3]), a[4:])
     elif cmd == "sweep":
         ab_sweep(int(a[0]), int(a[1]), int(a[2]), a[3], a[4:])
     elif cmd == "oja":
