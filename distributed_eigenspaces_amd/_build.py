@@ -17,8 +17,15 @@ SOURCES = ["capi.hip", "solver.hip", "syrk.hip", "syrk_split.hip", "syrk_u8.hip"
            "project.hip", "sweep.hip", "shift.hip", "procrustes.hip", "pca.hip", "pca_u8.hip", "syrk_bf16.hip", "pca_bf16.hip"]
 # Per-source extra flags.  sweep.hip: keep the split's scalar f32 subtractions
 # unpacked (v_pk_add_f32 beside MFMAs costs issue cycles, MI355X_MICROARCH.md).
-EXTRA_FLAGS = {"sweep.hip": ["-fno-slp-vectorize"], "syrk_split.hip": ["-fno-slp-vectorize"]}
-HEADERS = ["deig_internal.hpp", "skinny_tile.hpp", "syrk_image_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
+# pca_bf16.hip: the super-chunk loop of pca_packed_tile.hpp starts on a 64-byte instruction
+# line.  Left where the prologue's length puts it, the NB = 1 loop - instruction for
+# instruction the one from before the shared kernel - sat 24 bytes further up and ran 0.5 -
+# 0.9 % slower (k = 16); aligned, it runs as before.  The uint8 kernels measured no slower
+# than before as they fall, and 0.2 - 1 % slower aligned, so pca_u8.hip has no such flag
+# (profiles/pca_transform_packed_refactor.json).
+EXTRA_FLAGS = {"sweep.hip": ["-fno-slp-vectorize"], "syrk_split.hip": ["-fno-slp-vectorize"],
+               "pca_bf16.hip": ["-Xarch_device", "-falign-loops=64"]}
+HEADERS = ["deig_internal.hpp", "skinny_tile.hpp", "pca_packed_tile.hpp", "syrk_image_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
 # Test-only variant (tests/test_gpu_oja_timeout.py): oja.hip with a zero spin bound, so
 # every resident hand-off times out and the DEIG_ETIMEOUT report can be exercised; the
 # other objects are the shipped library's.

@@ -1,345 +1,94 @@
-// Fused centred transform of uint8 samples (deig_pca_transform_u8):
-//   Y = (V - 1 mean^T) W,   energy_i = ||v_i - mean||^2,   resid_i = max(0, energy_i - ||y_i||^2)
-// V the n x d feature matrix of the bytes X (DEIG_U8_RAW: v = x; DEIG_U8_GRAY3: v = (r + g + b)
-// / 3 of interleaved 3-byte pixels), mean: d doubles in units of v (NULL: no centring), W, Y,
-// resid, energy as deig_pca_transform_f32 (pca.hip).  The bytes are read once: a quarter
-// (raw) or three quarters (gray) of what the float kernel reads for the same features.
-//
-// The block tile, the W chunk's LDS store and the MFMA chunk product are skinny_tile.hpp's,
-// shared with pca_transform_kernel (pca.hip); the epilogue is that header's too, as text
-// (see the end of the kernel); no atomics.  This kernel's
-// own is how a chunk is staged (and with it which rows of W a chunk loads):
-//  * the float kernel gives 8 threads to a row and 16 B (4 floats) to a thread per 32-column
-//    chunk.  With bytes that map would load 4 B per thread and 32-B row segments.  Here the
-//    unit of loading is a SUPER-CHUNK of 128 features: 8 threads per row, 16 features per
-//    thread - one 16-B load (raw; three for the 48 B of gray), 128 (384) contiguous bytes per
-//    row, whole cache lines - held in registers and consumed by FOUR compute chunks;
-//  * compute chunk c of a super-chunk takes features 16 q + 4 c .. + 3 of every thread q:
-//    LDS slot 4 q + e of the chunk is feature 16 q + 4 c + e.  The order in which the d
-//    terms of a dot product are added does not matter as long as W's rows follow, and they
-//    do: slot s of the W chunk is row 16 (s >> 2) + 4 c + (s & 3) (each a contiguous kp-float
-//    row of the packed image, so the W loads stay coalesced).  Every thread converts one
-//    dword of each of its two rows per chunk - the float kernel's staging work per chunk, and
-//    an LDS budget just below its ((2 * 32 * 64 + 2 * 32 * bstride(kp)) floats: 20 KiB at
-//    kp = 16, 36 KiB at kp = 64 - four workgroups per CU - 84 KiB at kp = 256).  A
-//    128-feature chunk staged whole would need 4 x that (278 KiB of W alone at kp = 256,
-//    over the CU's 160 KiB);
-//  * the staged values sit in an XOR-swizzled layout (a_swz below) in which neither the
-//    staging writes nor the MFMA reads conflict on a bank; the float kernel's padded layout
-//    (row stride 80) puts the 8 staging threads of a row on one bank.  Measured in one run,
-//    the same kernel with that padded layout: 2.90 / 5.67 ms at k = 16 / 64 against 2.67 /
-//    5.22 ms (2^20 x 3072 raw bytes);
-//  * W's image and the mean are padded with zeros to whole super-chunks in the workspace, so
-//    the per-chunk loads carry no predicate on d, and the stage buffer of a chunk is its
-//    index's parity, a constant of the unrolled loop (immediate LDS offsets).  The staging is
-//    bound by instruction issue, not by memory (0.15 of HBM at k = 16): dropping those
-//    predicates and address updates took the raw call from 3.29 to 2.67 ms at k = 16;
-//  * the loads of super-chunk j + 1 are issued when super-chunk j's first chunk starts: three
-//    chunks of MFMA work to land in.
-// Centring at staging: t = fl32((double)v - mean), one rounding; gray v = (r + g + b) / 3.0
-// in double.  Rows past n and features past d stage exact zeros.  A last super-chunk with
-// fewer than 13 features left runs only the compute chunks that hold any (d % 128 in 4 ..
-// 12: 1 .. 3 chunks), so d = 4 costs one chunk; d = 36 costs four partly filled ones where
-// the float kernel has two - small d is not this kernel's case.
-#include "skinny_tile.hpp"
+// Fused centred transform of uint8 samples (deig_pca_transform_u8): pca_packed_tile.hpp's
+// kernel on two sources of bytes.  DEIG_U8_RAW: v = x; DEIG_U8_GRAY3: v = (r + g + b) / 3 of
+// interleaved 3-byte pixels, in double.  The bytes are read once: a quarter (raw) or three
+// quarters (gray) of what the float kernel reads for the same features.  A thread holds 16
+// features of a row per super-chunk of 128; d % 4 == 0, so the last one may be short.
+#include "pca_packed_tile.hpp"
 
 namespace deig {
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4_a4 __attribute__((aligned(4)));  // rows are only 4-byte aligned
+typedef ptile::u32x4 u32x4_a4 __attribute__((aligned(4)));  // rows are only 4-byte aligned
 
-constexpr int QBM = tile::kRows, QT = tile::kThreads;
-constexpr int QBK = tile::kChunk;  // LDS slots (features) per compute chunk
-constexpr int QSK = 4 * QBK;       // features per super-chunk (4 compute chunks)
-constexpr int QAST = QBM;          // row stride of a staged slot: no padding, XOR-swizzled rows
+template <int BPF>  // bytes per feature
+struct U8Source {
+  using Elem = uint8_t;
+  static constexpr int F = 16, DW = 4 * BPF, kXAlign = 4;
+  static constexpr bool kShortTail = true;
 
-// Staged values: slot sl (feature of the chunk) x row, at sl * QAST + (row ^ a_swz(sl)).
-// Both sides of the LDS are then free of bank conflicts (32 banks of 4 B per 32-lane half):
-//  * a staging write has e fixed and, per half, rows mm = m .. m + 3 with the 8 threads kq of
-//    each: sl = 4 kq + e, so the XOR with 4 kq (= sl & 28) spreads the 8 threads of a row over
-//    8 bank groups of 4 - 32 distinct banks (the float kernel's stride-80 layout puts those 8
-//    on ONE bank: 8-way);
-//  * an MFMA read has s fixed and, per half, kk = (0, 1) or (2, 3) with 16 rows r each:
-//    sl = 4 s + kk, sl & 28 = 4 s for both, and the XOR with (sl & 1) << 4 sends the odd kk to
-//    the other 16 banks.
-__device__ __forceinline__ int a_swz(int sl) { return (sl & 28) ^ ((sl & 1) << 4); }
-
-template <int NB, int MODE>
-__global__ __launch_bounds__(QT) void pca_transform_u8_kernel(
-    const uint8_t* __restrict__ X, int64_t ldx, const double* __restrict__ mean,
-    const float* __restrict__ Wr, float* __restrict__ Y, int64_t ldy, float* __restrict__ resid,
-    float* __restrict__ energy, int64_t n, int64_t d, int k) {
-  constexpr int N = NB * 16;
-  constexpr int KA = NB == 1 ? 2 : 1;  // accumulators per fragment
-  constexpr int BST = tile::bstride(N);
-  constexpr int NB4 = QBK * N / 4, BPT = tile::b_per_thread(NB);  // float4s per chunk, per thread
-  constexpr int BPF = MODE == DEIG_U8_GRAY3 ? 3 : 1;  // bytes per feature
-  constexpr int DW = 4 * BPF;  // dwords a thread holds per row and super-chunk
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                   // [2][QBK][QAST]
-  float* Bs = smem + 2 * QBK * QAST;  // [2][QBK][BST]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t m0 = (int64_t)blockIdx.x * QBM;
-  const int64_t nsc = (d + QSK - 1) / QSK;
-  // staging map: thread -> rows mm and mm + 32 of the tile, features 16 kq .. 16 kq + 15 of a
-  // super-chunk
-  const int mm = tid >> 3, kq = tid & 7;
-  const bool rowlive[2] = {m0 + mm < n, m0 + mm + 32 < n};
-
-  f32x4 acc[NB][KA];
+  // one aligned-to-4 16-B load per BPF when all 16 features lie inside d, else dword by
+  // dword for the 4-feature groups that do (d % 4 == 0: in or out together)
+  static __device__ __forceinline__ void load(const uint8_t* row, bool live, int64_t kc, int64_t d,
+                                              uint32_t (&x)[DW]) {
 #pragma unroll
-  for (int j = 0; j < NB; ++j)
+    for (int w = 0; w < DW; ++w) x[w] = 0u;
+    if (live && kc < d) {
+      const uint8_t* p = row + BPF * kc;
+      if (kc + 16 <= d) {
 #pragma unroll
-    for (int a = 0; a < KA; ++a) acc[j][a] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  uint32_t xa[2][DW], xb[2][DW];  // this and the next super-chunk's bytes
-  f32x4 rb[BPT];
-  double mu[4] = {0.0, 0.0, 0.0, 0.0};
-  float en[2] = {0.f, 0.f};
-
-  // 16 features of two rows: one aligned-to-4 16-B load per BPF when all 16 lie inside d,
-  // else dword by dword for the 4-feature groups that do (d % 4 == 0: in or out together) -
-  // nothing past column d of a row is ever read
-  auto load_x = [&](int64_t sc, uint32_t (&x)[2][DW]) {
-    const int64_t kc = sc * QSK + 16 * kq;
+        for (int q = 0; q < BPF; ++q) {
+          const ptile::u32x4 v = *reinterpret_cast<const u32x4_a4*>(p + 16 * q);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+          for (int w = 0; w < 4; ++w) x[4 * q + w] = v[w];
+        }
+      } else {
 #pragma unroll
-      for (int w = 0; w < DW; ++w) x[u][w] = 0u;
-      if (rowlive[u] && kc < d) {
-        const uint8_t* p = X + (m0 + mm + 32 * u) * ldx + BPF * kc;
-        if (kc + 16 <= d) {
+        for (int g = 0; g < 4; ++g)
+          if (kc + 4 * g < d) {
 #pragma unroll
-          for (int q = 0; q < BPF; ++q) {
-            const u32x4 v = *reinterpret_cast<const u32x4_a4*>(p + 16 * q);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) x[u][4 * q + w] = v[w];
+            for (int w = 0; w < BPF; ++w)
+              x[BPF * g + w] = *reinterpret_cast<const uint32_t*>(p + 4 * (BPF * g + w));
           }
-        } else {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            if (kc + 4 * g < d) {
-#pragma unroll
-              for (int w = 0; w < BPF; ++w)
-                x[u][BPF * g + w] = *reinterpret_cast<const uint32_t*>(p + 4 * (BPF * g + w));
-            }
-        }
       }
-    }
-  };
-  // chunk c of super-chunk sc: this thread's mean entries and its share of the W chunk.
-  // Both come from images padded with zeros to a whole super-chunk (pca_transform_u8_launch):
-  // no predicate on d here, and a feature past d stages fl32(0 - 0) = 0 by itself.
-  auto load_wm = [&](int64_t sc, int c) {
-    const int64_t kb = sc * QSK;
-    const int64_t kc = kb + 16 * kq + 4 * c;
-    if (mean) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) mu[e] = mean[kc + e];
-    }
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      const int f = tid + QT * u;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (f < NB4) {
-        const int slot = f / (N / 4), c4 = f % (N / 4);
-        const int64_t kr = kb + 16 * (slot >> 2) + 4 * c + (slot & 3);
-        v = *reinterpret_cast<const f32x4*>(Wr + kr * N + 4 * c4);
-      }
-      rb[u] = v;
-    }
-  };
-  // centring happens here: t = fl32(v - mean) in double, one rounding; rows past n are set
-  // to zero, features past d are zero bytes against a zero mean
-  auto store = [&](int buf, const uint32_t (&x)[2][DW], int c) {
-    float* as = As + buf * QBK * QAST;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float t;
-        if (MODE == DEIG_U8_RAW) {
-          const float v = (float)((x[u][c] >> (8 * e)) & 0xffu);  // one byte-to-float convert
-          t = mean ? (float)((double)v - mu[e]) : v;
-        } else {
-          uint32_t s = 0;
-#pragma unroll
-          for (int b = 0; b < 3; ++b) {
-            const int byte = 3 * e + b;
-            s += (x[u][3 * c + (byte >> 2)] >> (8 * (byte & 3))) & 0xffu;
-          }
-          // s / 3.0, correctly rounded, without the division's expansion: q = s * fl(1/3)
-          // is within an ulp, the residual fma(-3, q, s) is exact, and one correction step
-          // lands on the rounded quotient (equal to s / 3.0 for every s in 0 .. 765: checked
-          // exhaustively on the host)
-          const double sd = (double)s, third = 1.0 / 3.0;
-          const double q = sd * third;
-          const double v = fma(fma(-3.0, q, sd), third, q);
-          t = mean ? (float)(v - mu[e]) : (float)v;
-        }
-        if (!rowlive[u]) t = 0.f;
-        en[u] = fmaf(t, t, en[u]);
-        as[(4 * kq + e) * QAST + ((mm + 32 * u) ^ a_swz(4 * kq + e))] = t;
-      }
-    }
-    tile::store_b<NB>(Bs + buf * QBK * BST, rb, tid);
-  };
-
-  const int r = lane & 15, kk = lane >> 4;
-  const int arow = (16 * wave + r) ^ ((kk & 1) << 4);  // this lane's A row, swizzled but for 4 s
-  load_x(0, xa);
-  load_wm(0, 0);
-  store(0, xa, 0);
-  __syncthreads();
-  // the stage buffer of chunk c is c & 1: every super-chunk but the last runs 4 chunks, so
-  // the parity is a compile-time constant of the unrolled loop (immediate LDS offsets)
-  for (int64_t sc = 0; sc < nsc; ++sc) {
-    const bool msc = sc + 1 < nsc;
-    if (msc) load_x(sc + 1, xb);
-    // compute chunks of this super-chunk that hold any feature (4 but for a short tail)
-    const int64_t left = d - sc * QSK;
-    const int ncs = left >= 16 ? 4 : (int)(left / 4);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c < ncs) {
-        const bool within = c + 1 < ncs;
-        const bool more = within || msc;
-        if (more) {
-          if (within)
-            load_wm(sc, c + 1);
-          else
-            load_wm(sc + 1, 0);
-        }
-        const int cur = c & 1;
-        const float* as = As + cur * QBK * QAST + kk * QAST;
-        // a_swz(4 s + kk), kk's bit in arow
-        tile::mfma_chunk(acc, Bs + cur * QBK * BST, r, kk,
-                         [&](int s) { return as[4 * s * QAST + (arow ^ (4 * s))]; });
-        if (more) {
-          if (within)
-            store(cur ^ 1, xa, (c + 1) & 3);
-          else
-            store(cur ^ 1, xb, 0);
-        }
-        __syncthreads();
-      }
-    }
-    if (msc) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int w = 0; w < DW; ++w) xa[u][w] = xb[u][w];
     }
   }
+};
 
-  // The text of tile::transform_epilogue.  Called as the helper, this kernel's K loop issues
-  // one of the staging's packed energy fmas (v_pk_fma_f32) as two scalar ones.
-  float* es = smem;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    float e = en[u];
-    e += __shfl_xor(e, 1);
-    e += __shfl_xor(e, 2);
-    e += __shfl_xor(e, 4);
-    if (kq == 0) es[mm + 32 * u] = e;
+struct U8Raw : U8Source<1> {
+  static __device__ __forceinline__ float value(const uint32_t (&x)[DW], int c, int e, bool centred,
+                                                double mu) {
+    const float v = (float)((x[c] >> (8 * e)) & 0xffu);  // one byte-to-float convert
+    return centred ? (float)((double)v - mu) : v;
   }
-  __syncthreads();
+};
 
-  const int lrow = 16 * wave + 4 * kk;
+struct U8Gray3 : U8Source<3> {
+  static __device__ __forceinline__ float value(const uint32_t (&x)[DW], int c, int e, bool centred,
+                                                double mu) {
+    uint32_t s = 0;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int64_t m = m0 + lrow + e;
-    float yn = 0.f;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      float v = acc[j][0][e];
-      if (KA == 2) v += acc[j][KA - 1][e];
-      yn = fmaf(v, v, yn);  // columns >= k are exactly zero (zero-padded W image)
-      if (Y && m < n && 16 * j + r < k) Y[m * ldy + 16 * j + r] = v;
+    for (int b = 0; b < 3; ++b) {
+      const int byte = 3 * e + b;
+      s += (x[3 * c + (byte >> 2)] >> (8 * (byte & 3))) & 0xffu;
     }
-    yn += __shfl_xor(yn, 1);
-    yn += __shfl_xor(yn, 2);
-    yn += __shfl_xor(yn, 4);
-    yn += __shfl_xor(yn, 8);
-    if (r == 0 && m < n) {
-      const float ev = es[lrow + e];
-      if (energy) energy[m] = ev;
-      if (resid) resid[m] = fmaxf(0.f, ev - yn);
-    }
+    // s / 3.0, correctly rounded, without the division's expansion: q = s * fl(1/3) is
+    // within an ulp, the residual fma(-3, q, s) is exact, and one correction step lands on
+    // the rounded quotient (equal to s / 3.0 for every s in 0 .. 765: checked exhaustively
+    // on the host)
+    const double sd = (double)s, third = 1.0 / 3.0;
+    const double q = sd * third;
+    const double v = fma(fma(-3.0, q, sd), third, q);
+    return centred ? (float)(v - mu) : (float)v;
   }
-}
-
-// mean -> a copy padded with zeros to dpad entries
-__global__ __launch_bounds__(256) void pad_mean_kernel(const double* __restrict__ mean, int64_t d,
-                                                       int64_t dpad, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < dpad) out[i] = i < d ? mean[i] : 0.0;
-}
-
-template <int MODE>
-int pca_u8_dispatch(int kp, const uint8_t* X, int64_t ldx, const double* mean, const float* Wr,
-                    float* Y, int64_t ldy, float* resid, float* energy, int64_t n, int64_t d, int k,
-                    hipStream_t st) {
-  const dim3 grid((unsigned)cdiv(n, QBM));
-  const int rc = tile::dispatch_nb(kp / 16, [&](auto nb) {
-    return tile::launch<pca_transform_u8_kernel<nb(), MODE>>(
-        grid, tile::shm_bytes(nb() * 16, QAST), st, X, ldx, mean, Wr, Y, ldy, resid, energy, n, d, k);
-  });
-  if (rc == tile::kNoSuchNb) return fail(DEIG_EINVAL, "pca_transform_u8: unsupported k = %d", k);
-  return rc;
-}
+};
 
 }  // namespace
 
-// Workspace: the packed W image and the mean, both padded with zeros to whole super-chunks.
-static size_t pca_u8_mean_off(int64_t dpad, int kp) {
-  return align_up((size_t)dpad * kp * sizeof(float), 256);
-}
-
 size_t pca_transform_u8_workspace_bytes(int64_t n, int64_t d, int k) {
-  if (n < 1 || d < 1 || k < 1 || k > 256) return 0;
-  const int64_t dpad = cdiv(d, QSK) * QSK;
-  const int kp = (int)cdiv(k, 16) * 16;
-  return pca_u8_mean_off(dpad, kp) + align_up((size_t)dpad * sizeof(double), 256);
+  return ptile::workspace_bytes(n, d, k, ptile::kSuper<U8Raw>);
 }
 
 int pca_transform_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
                             const double* mean, const float* W, int k, int64_t ldw, float* Y,
                             int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
                             hipStream_t st) {
-  DEIG_REQUIRE(k >= 1 && k <= 256, "pca_transform_u8: k=%d must be in 1..256", k);
-  if (int rc = u8_check_shape("pca_transform_u8", n, d, ldx, mode, int64_t(1) << 31)) return rc;
-  DEIG_REQUIRE(ldw >= d, "pca_transform_u8: ldw must be >= d");
-  DEIG_REQUIRE(Y || resid || energy,
-               "pca_transform_u8: need at least one output (Y, resid, energy)");
-  DEIG_REQUIRE(!Y || ldy >= k, "pca_transform_u8: ldy must be >= k");
-  DEIG_REQUIRE(X && (reinterpret_cast<uintptr_t>(X) & 3u) == 0 && W,
-               "pca_transform_u8: X (4-byte aligned) and W must not be NULL");
-  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(mean) % 8 == 0,
-               "pca_transform_u8: mean must be 8-byte aligned");
-  const size_t need = pca_transform_u8_workspace_bytes(n, d, k);
-  if (!ws || ws_bytes < need)
-    return fail(DEIG_EWORKSPACE, "pca_transform_u8: workspace %zu bytes < required %zu", ws_bytes,
-                need);
-  const int kp = (int)cdiv(k, 16) * 16;
-  const int64_t dpad = cdiv(d, QSK) * QSK;
-  float* Wr = static_cast<float*>(ws);
-  if (int rc = pack_w_launch(W, ldw, d, k, kp, Wr, st)) return rc;
-  if (dpad > d)
-    DEIG_HIP_CHECK(hipMemsetAsync(Wr + d * kp, 0, sizeof(float) * (size_t)(dpad - d) * kp, st));
-  double* mpad = nullptr;
-  if (mean) {
-    mpad = reinterpret_cast<double*>(static_cast<char*>(ws) + pca_u8_mean_off(dpad, kp));
-    hipLaunchKernelGGL(pad_mean_kernel, dim3((unsigned)cdiv(dpad, 256)), dim3(256), 0, st, mean, d, dpad,
-                       mpad);
-    DEIG_HIP_CHECK(hipGetLastError());
-  }
+  const char* what = "pca_transform_u8";
+  auto check = [&] { return u8_check_shape(what, n, d, ldx, mode, int64_t(1) << 31); };
   if (mode == DEIG_U8_RAW)
-    return pca_u8_dispatch<DEIG_U8_RAW>(kp, X, ldx, mpad, Wr, Y, ldy, resid, energy, n, d, k, st);
-  return pca_u8_dispatch<DEIG_U8_GRAY3>(kp, X, ldx, mpad, Wr, Y, ldy, resid, energy, n, d, k, st);
+    return ptile::launch<U8Raw>(what, X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws,
+                                ws_bytes, st, check);
+  return ptile::launch<U8Gray3>(what, X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws,
+                                ws_bytes, st, check);  // an unknown mode: check's to report
 }
 
 }  // namespace deig

@@ -1,7 +1,8 @@
 // The block tile shared by skinny_kernel (skinny.hip), pca_transform_kernel (pca.hip) and
-// pca_transform_u8_kernel (pca_u8.hip), stated once: the layout and its reasons, the tile
-// constants and LDS sizing, the B chunk store, the MFMA chunk product and the host-side
-// dispatch and launch (all three kernels), and the transform epilogue (the PCA kernels).
+// pca_transform_packed_kernel (pca_packed_tile.hpp: uint8 and bf16 samples), stated once: the
+// layout and its reasons, the tile constants and LDS sizing, the B chunk store, the MFMA chunk
+// product and the host-side dispatch and launch (all three kernels), and the transform
+// epilogue (pca_transform_kernel calls it; the packed kernel carries its text, see there).
 //
 // Tile.  A block of kThreads = 4 waves owns kRows = 64 rows x N = 16 NB columns of the
 // output; wave w owns rows 16 w .. 16 w + 15 as NB accumulator fragments of
@@ -9,7 +10,8 @@
 // chunk's two operands are loaded into registers, then written to LDS after the products
 // of the chunk before it (two stage buffers), as k-major images:
 //   A [slot][row], row stride chosen by the kernel: kAStridePadded (80) in the float
-//     kernels, 64 with XOR-swizzled rows in the byte kernel (a_swz, pca_u8.hip);
+//     kernels, 64 with XOR-swizzled rows in the packed-sample kernel (a_swz,
+//     pca_packed_tile.hpp);
 //   B [slot][column], row stride bstride(N).
 // LDS per block: shm_bytes(N, a_stride).
 //

@@ -471,13 +471,13 @@ def _pad_vector(v, d: int, dp: int, device, name: str):
     return v.contiguous()
 
 
-def _transform_operands(W, d, dp, mean, dev, wname: str):
+def _transform_operands(W, d, dp, mean, dev, wname: str, multiple: int = 4):
     """The W and mean operands of ``project`` and the PCA transforms: ``(W, mean, k)`` with
     W (checked: 2-D, 1 <= k <= 256, rows matching the samples) zero-padded to dp rows and
     column-major, mean as ``_pad_vector`` gives it on ``dev``.  d: the number of features
     when the samples fix it (uint8); None when W's rows do, the samples having dp columns
-    (d itself, or d rounded up to a multiple of 4).  The padding rows and entries are zero:
-    they meet zero columns of the samples."""
+    (d itself, or d rounded up to a multiple of ``multiple``: 4 floats, 8 bfloat16).  The
+    padding rows and entries are zero: they meet zero columns of the samples."""
     W = require_device_tensor(W, wname)
     if W.dim() != 2:
         raise ValueError(f"{wname} must be 2-D (d, k), got shape {tuple(W.shape)}")
@@ -486,7 +486,7 @@ def _transform_operands(W, d, dp, mean, dev, wname: str):
         raise ValueError(f"k={k} out of range [1, 256]")
     if d is None:
         d = rows
-        if d > dp or (dp != d and dp != (d + 3) // 4 * 4):
+        if d > dp or (dp != d and dp != -(-d // multiple) * multiple):
             raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
     elif rows != d:
         raise ValueError(f"shape mismatch: X has {d} features, W has {rows} rows")
@@ -1167,13 +1167,7 @@ def _pca_transform_bf16(X, W, mean, residual: bool, energy: bool):
     X = _rowmajor_8_bf16(bf16_device_tensor(X, "pca_transform"), "X")
     n, dp = X.shape
     dev = X.device
-    W = require_device_tensor(W, "W")
-    if W.dim() != 2:
-        raise ValueError(f"W must be 2-D (d, k), got shape {tuple(W.shape)}")
-    d = W.shape[0]
-    if d > dp or (dp != d and dp != (d + 7) // 8 * 8):
-        raise ValueError(f"shape mismatch: X has {dp} columns, W has {d} rows")
-    W, mu, k = _transform_operands(W, d, dp, mean, dev, "W")
+    W, mu, k = _transform_operands(W, None, dp, mean, dev, "W", multiple=8)
     Y, res, en = _transform_buffers(n, k, dev, residual, energy)
     if n > 0:
         _call(dev, "deig_pca_transform_bf16",

@@ -91,6 +91,23 @@ def test_transform_argument_rules():
         assert L.deig_pca_transform_bf16_workspace(1 << 20, 3072, k) >= 3072 * kp * 4
 
 
+def _align(x, a):
+    return (x + a - 1) // a * a
+
+
+# the packed W image (dpad x kp floats) and the padded mean (dpad doubles), each a 256-byte
+# aligned slice, dpad = d rounded up to a super-chunk of 64 features
+@pytest.mark.parametrize("n,d,k,want", [(1, 8, 1, 4608), (1000, 264, 17, 43520),
+                                        (1 << 20, 3072, 256, 3170304)])
+def test_transform_workspace_is_exact(n, d, k, want):
+    L = _lib.lib()
+    dpad, kp = _align(d, 64), _align(k, 16)
+    assert want == _align(dpad * kp * 4, 256) + _align(dpad * 8, 256)
+    assert L.deig_pca_transform_bf16_workspace(n, d, k) == want
+    assert L.deig_pca_transform_bf16_workspace(n, d, 0) == 0
+    assert L.deig_pca_transform_bf16_workspace(n, d, 257) == 0
+
+
 def test_column_passes_know_bf16_and_reject_unknown_types():
     L = _lib.lib()
     # an odd address is misaligned for every type; bf16 needs 2 bytes only

@@ -1,5 +1,6 @@
-"""The bits of the three kernels built on the shared tile (csrc/skinny_tile.hpp) are pinned:
-``pca_transform``, ``pca_transform_u8`` and ``gemm_skinny`` must return exactly what
+"""The bits of the kernels built on the shared tile (csrc/skinny_tile.hpp) are pinned:
+``pca_transform`` (float32 and bfloat16 samples), ``pca_transform_u8`` and ``gemm_skinny``
+must return exactly what
 tests/golden/transform_bits.npz recorded on an MI355X.  The kernels use no atomics and add
 in a fixed order, so equal bits are what "behaviour unchanged" means for them; the accuracy
 of the same calls is tested against float64 in test_gpu_pca_kernels.py,
@@ -12,7 +13,14 @@ Each case is the smallest shape that reaches one path of the tile:
   mean, the padded W stride; (65, 132, 256) NB = 16;
 * pca_transform_u8: raw (65, 36, 3) four partly filled compute chunks, with and without a
   mean; raw (129, 260, 17) a last super-chunk of one chunk; raw (64, 132, 256); gray
-  (129, 260, 17);
+  (129, 260, 17); raw (65, 136, 16) and (65, 140, 16) a last super-chunk of two and of
+  three chunks; gray (65, 44, 3) without a mean, the dword tail load at three 4-feature
+  groups;
+* pca_transform of bfloat16 samples (the float32 values 100 + 3 randn with their low 16
+  bits cleared, so the conversion is exact): (65, 72, 3) a row-tile tail, one whole
+  super-chunk and one of 8 features, NB = 1 with its two accumulators; (129, 264, 17)
+  k < kp, NB = 2; (63, 1032, 64) without a mean; (64, 136, 256) NB = 16; (65, 8, 3) a
+  single super-chunk whose second chunk is all zeros, without a mean;
 * gemm_skinny (M, N, K) on normal data with alpha = 1.5, beta = 0.5, both forms, split-K
   in two slices.  The split factor depends on the number of CUs, so these two skip on a
   device whose count differs from the recorded one.
@@ -36,7 +44,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "transform_bits.npz")
 
-# (kind, shape, with mean) - kind "f32" / "raw" / "gray": (n, d, k); "gemmN" / "gemmT": (M, N, K)
+# (kind, shape, with mean) - kind "f32" / "raw" / "gray" / "bf16": (n, d, k); "gemmN" / "gemmT": (M, N, K)
 CASES = [
     ("f32", (65, 36, 3), True),
     ("f32", (129, 260, 17), True),
@@ -49,6 +57,14 @@ CASES = [
     ("raw", (65, 36, 3), False),
     ("gemmN", (130, 48, 516), False),
     ("gemmT", (132, 48, 516), False),
+    ("bf16", (65, 72, 3), True),
+    ("bf16", (129, 264, 17), True),
+    ("bf16", (63, 1032, 64), False),
+    ("bf16", (64, 136, 256), True),
+    ("bf16", (65, 8, 3), False),
+    ("raw", (65, 136, 16), True),
+    ("raw", (65, 140, 16), True),
+    ("gray", (65, 44, 3), False),
 ]
 ALPHA, BETA = 1.5, 0.5
 
@@ -68,8 +84,10 @@ def make_inputs(index, case):
                 "B": rng.standard_normal((K, N)).astype(np.float32),
                 "C": rng.standard_normal((M, N)).astype(np.float32)}
     n, d, k = a, b, c
-    if kind == "f32":
+    if kind in ("f32", "bf16"):
         X = (100.0 + 3.0 * rng.standard_normal((n, d))).astype(np.float32)
+        if kind == "bf16":  # bf16 values held as float32: the low 16 bits cleared
+            X.view(np.uint32)[...] &= np.uint32(0xffff0000)
         centre = 100.0
     else:
         X = rng.integers(0, 256, (n, 3 * d if kind == "gray" else d), dtype=np.uint8)
@@ -95,7 +113,9 @@ def run_case(case, inputs, dev):
     t = {name: torch.from_numpy(a).to(dev) for name, a in inputs.items()}
     if kind.startswith("gemm"):
         return {"C": linalg.gemm_skinny(t["A"], t["B"], kind == "gemmT", ALPHA, BETA, C=t["C"])}
-    if kind == "f32":
+    if kind in ("f32", "bf16"):
+        if kind == "bf16":
+            t["X"] = t["X"].to(torch.bfloat16)  # exact: make_inputs cleared the low bits
         out = linalg.pca_transform(t["X"], t["W"], t.get("mean"), residual=True, energy=True)
     else:
         out = linalg.pca_transform_u8(t["X"], t["W"], t.get("mean"), kind, residual=True,

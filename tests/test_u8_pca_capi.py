@@ -33,6 +33,23 @@ def test_workspace_queries(n, d):
         assert L.deig_pca_transform_u8_workspace(n, d, k) >= d * kp * 4 > 0  # the packed W image
 
 
+def _align(x, a):
+    return (x + a - 1) // a * a
+
+
+# the packed W image (dpad x kp floats) and the padded mean (dpad doubles), each a 256-byte
+# aligned slice, dpad = d rounded up to a super-chunk of 128 features
+@pytest.mark.parametrize("n,d,k,want", [(1, 4, 1, 9216), (1000, 260, 17, 52224),
+                                        (1 << 20, 3072, 256, 3170304)])
+def test_transform_workspace_is_exact(n, d, k, want):
+    L = _lib.lib()
+    dpad, kp = _align(d, 128), _align(k, 16)
+    assert want == _align(dpad * kp * 4, 256) + _align(dpad * 8, 256)
+    assert L.deig_pca_transform_u8_workspace(n, d, k) == want
+    assert L.deig_pca_transform_u8_workspace(n, d, 0) == 0
+    assert L.deig_pca_transform_u8_workspace(n, d, 257) == 0
+
+
 # NULL pointers everywhere: the argument rules come first, nothing touches a GPU
 def _colsum(n=8, d=16, ldx=16, mode=RAW):
     return _lib.lib().deig_colsum_u8(None, n, d, ldx, mode, None, None, 0, None)

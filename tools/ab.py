@@ -10,6 +10,7 @@ in-tree distributed_eigenspaces_amd/libdeig.so.
   python tools/ab.py build "MACRO=V [-DOTHER=W]" tools/ab_libs/libdeig_x.so   # here (CPU)
   python tools/ab.py syrk  REPS N D LIB [LIB ...]          # split3 covariance, ms per op
   python tools/ab.py cov   KIND REPS N D LIB [LIB ...]     # KIND u8raw | u8gray | bf16, us per op
+  python tools/ab.py transform KIND REPS N D K LIB [LIB ...]   # fused PCA transform, KIND as cov
   python tools/ab.py sweep REPS D P MODE LIB [LIB ...]     # solver sweep chain, us per sweep
                                                            # MODE half | bf16x3 | bf16x5 | bf16x6
   python tools/ab.py oja   REPS ORTH LIB [LIB ...]         # config-4 Oja, us per batch
@@ -138,7 +139,6 @@ def ab_cov(kind, reps, n, d, paths):
     (deig_syrk_bf16).  A refactor's check lists the parent build twice (two file copies A, A')
     and then the new build: the gap between the two parent medians is what the run cannot
     resolve, and the JSON line says whether each later build is within it."""
-    import json
     import torch
     from distributed_eigenspaces_amd import _lib, synthetic
     libs = load_libs(paths)
@@ -174,15 +174,76 @@ def ab_cov(kind, reps, n, d, paths):
 
     times, outs = interleave(libs, reps, run)
     ref = outs[libs[0][0]]
-    report(times, lambda p: torch.equal(outs[p], ref), f"us ({kind} {n} x {d})")
+    report_json(times, lambda p: torch.equal(outs[p], ref), f"us ({kind} {n} x {d})", paths,
+                {"kind": kind, "n": n, "d": d, "reps": reps})
+
+
+def report_json(times, same, unit, paths, shape):
+    """report(), then one JSON line: shape's fields, the medians, bit identity to the first
+    build and, from three builds on, the gap of the first two and who is within it."""
+    import json
+    report(times, same, unit)
     med = {p: statistics.median(ts) for p, ts in times.items()}
-    res = {"kind": kind, "n": n, "d": d, "reps": reps, "median_us": {p: round(m, 2) for p, m in med.items()},
-           "bit_identical_to_first": {p: bool(torch.equal(outs[p], ref)) for p in med}}
+    res = dict(shape, median_us={p: round(m, 2) for p, m in med.items()},
+               bit_identical_to_first={p: bool(same(p)) for p in med})
     if len(paths) >= 3:
         a, a2 = med[paths[0]], med[paths[1]]
         res["gap_us"] = round(abs(a - a2), 2)
         res["within_gap"] = {p: bool(med[p] <= max(a, a2) + abs(a - a2)) for p in paths[2:]}
     print("JSON " + json.dumps(res), flush=True)
+
+
+# ---------------------------------------------------------------- transform (uint8, bf16 samples)
+def ab_transform(kind, reps, n, d, k, paths):
+    """Fused centred transform of uint8 (u8raw | u8gray: deig_pca_transform_u8) or bf16 samples
+    (deig_pca_transform_bf16), with a mean and all three outputs; builds listed as for cov."""
+    import torch
+    from distributed_eigenspaces_amd import _lib, synthetic
+    libs = load_libs(paths)
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(7)
+    if kind == "bf16":
+        U = synthetic.planted_basis(d, 64 if d >= 64 else d, 0, dev)
+        X = synthetic.spiked_samples(n, U, seed=1).to(torch.bfloat16)
+        query, centre = "deig_pca_transform_bf16_workspace", 0.0
+    else:
+        # bytes around 128 with a spread of 30 (any d: spiked_bytes' pixels need a square image)
+        mode = _lib.U8_MODES[kind[2:]]
+        X = torch.empty((n, 3 * d if kind == "u8gray" else d), dtype=torch.uint8, device=dev)
+        for lo in range(0, n, 1 << 16):
+            blk = X[lo:lo + (1 << 16)]
+            blk.copy_(torch.randn(blk.shape, generator=g, device=dev).mul_(30.0).add_(128.0).clamp_(0, 255))
+        query, centre = "deig_pca_transform_u8_workspace", 127.5
+    W = torch.linalg.qr(torch.randn(d, k, generator=g, device=dev))[0].t().contiguous().t()  # column-major
+    mean = centre + torch.randn(d, generator=g, device=dev, dtype=torch.float64)
+    nbytes = max(getattr(L, query)(n, d, k) for _, L in libs)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    out = {p: (torch.empty(n, k, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev))
+           for p, _ in libs}
+    st = torch.cuda.current_stream(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    inner = 20 if n * d < 1e9 else 1  # short shapes: time a run of calls
+
+    def run(path, L):
+        Y, res, en = out[path]
+        tail = (mean.data_ptr(), W.data_ptr(), k, W.stride(1), Y.data_ptr(), k, res.data_ptr(),
+                en.data_ptr(), ws.data_ptr(), nbytes, st.cuda_stream)
+        torch.cuda.synchronize()
+        e0.record(st)
+        for _ in range(inner):
+            if kind == "bf16":
+                rc = L.deig_pca_transform_bf16(X.data_ptr(), n, d, X.stride(0), *tail)
+            else:
+                rc = L.deig_pca_transform_u8(X.data_ptr(), n, d, X.stride(0), mode, *tail)
+            assert rc == 0, L.deig_last_error()
+        e1.record(st)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / inner * 1e3, out[path]
+
+    times, outs = interleave(libs, reps, run)
+    ref = outs[libs[0][0]]
+    report_json(times, lambda p: all(torch.equal(a, b) for a, b in zip(outs[p], ref)),
+                f"us ({kind} {n} x {d}, k = {k})", paths, {"kind": kind, "n": n, "d": d, "k": k, "reps": reps})
 
 
 # ---------------------------------------------------------------- sweep
@@ -361,6 +422,8 @@ def main(argv):
         ab_syrk(int(a[0]), int(a[1]), int(a[2]), a[3:])
     elif cmd == "cov":
         ab_cov(a[0], int(a[1]), int(a[2]), int(a[3]), a[4:])
+    elif cmd == "transform":
+        ab_transform(a[0], int(a[1]), int(a[2]), int(a[3]), int(a[4]), a[5:])
     elif cmd == "sweep":
         ab_sweep(int(a[0]), int(a[1]), int(a[2]), a[3], a[4:])
     elif cmd == "oja":
