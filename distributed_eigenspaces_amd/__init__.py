@@ -19,7 +19,10 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
                      pca_transform, the estimator and PCA take bfloat16 without widening it
   * oja_step(s)    - mini-batch Oja (online variant, config 4); streaming.StreamingOja
                      adds the periodic all-gather / server solve / broadcast; bfloat16
-                     batches are read as bfloat16 (two-product kernels, no float32 copy)
+                     batches are read as bfloat16 (two-product kernels, no float32 copy);
+                     ``center=`` takes the steps about a centre on float32, bfloat16 and uint8
+                     batches read in place (centred where the kernels stage a sample), and
+                     StreamingOja(center=...) keeps a fixed or a running pooled mean
 
 Drop-in modules: ``distributed`` (Node / SlaveNode / MasterNode / run_* / main),
 ``my_threading`` (Slave) and ``notebook`` (make_batches, top_k_eigenvectors,

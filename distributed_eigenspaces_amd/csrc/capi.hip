@@ -516,6 +516,14 @@ int deig_oja_steps_bf16(const void* X, int64_t nb, int64_t b, int64_t d, int64_t
                                (hipStream_t)stream);
 }
 
+int deig_oja_steps_centered(const void* X, int xtype, int64_t nb, int64_t b, int64_t d, int64_t ldx,
+                            const double* center, float eta, float* V, int k, int64_t ldv,
+                            int orth_every, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return oja_steps_centered_launch(X, xtype, nb, b, d, ldx, center, eta, V, k, ldv, orth_every, ws,
+                                   ws_bytes, (hipStream_t)stream);
+}
+
 int deig_oja_step_f32(const float* Xb, int64_t b, int64_t d, int64_t ldx, float eta, float* V,
                       int k, int64_t ldv, void* ws, size_t ws_bytes, void* stream) {
   g_err[0] = 0;

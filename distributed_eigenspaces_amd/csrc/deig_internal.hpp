@@ -268,6 +268,9 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
 int oja_steps_bf16_launch(const void* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
                           float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
                           hipStream_t stream);
+int oja_steps_centered_launch(const void* X, int xtype, int64_t nb, int64_t b, int64_t d, int64_t ldx,
+                              const double* center, float eta, float* V, int k, int64_t ldv,
+                              int orth_every, void* ws, size_t ws_bytes, hipStream_t stream);
 int oja_error(const void* ws, size_t ws_bytes, int64_t b, int64_t d, int k, hipStream_t st);
 
 // Projection Y = X W (project.hip).

@@ -11,6 +11,10 @@
 // bf16 samples (deig_oja_steps_bf16) run the two-pass kernels instantiated on the sample
 // type: a bf16 value is its own hi piece, so two MFMAs per fragment pair instead of three
 // and half the bytes of Xb, with the bits of the float kernels on the widened samples.
+// deig_oja_steps_centered adds raw bytes as a third sample type (exact in bf16: two MFMAs,
+// a quarter of the bytes) and a centred variant of every loader: the staged value is
+// fl32((double)x - mean[j]), one rounding, split into hi / lo (three MFMAs whatever the
+// sample type), with the bits of the float kernels on the matrix of those staged values.
 #include <algorithm>
 #include <type_traits>
 
@@ -252,34 +256,75 @@ __global__ __launch_bounds__(256) void trsm_img_kernel(const float* __restrict__
 // the same k-steps in the same order, hence the bits of the float kernels on the widened
 // samples, from half the bytes.
 typedef __bf16 OjaBf16;
+// Raw bytes (DEIG_U8): a byte is exact in bf16, so, like a bf16 sample, it is its own hi piece
+// with a zero lo piece.  d % 4 == 0 and 4-byte alignment are all a row promises: 4-byte loads.
+typedef uint8_t OjaU8;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
+__device__ __forceinline__ float oja_byte(uint32_t w, int e) { return (float)((w >> (8 * e)) & 0xffu); }
+// Centring at staging (ptile::Src::value): formed in double, rounded once.
+__device__ __forceinline__ float oja_centre(float x, double mu) { return (float)((double)x - mu); }
+
 // NN operand: a lane's 8 consecutive features of one row (p: the row, k: first feature,
-// clamped so that nothing behind column d is read) and its A fragments.
+// clamped so that nothing behind column d is read) and its A fragments.  kGroup: the
+// features that one clamp covers (feature e of the lane is column
+// min(k + kGroup (e / kGroup), d - kGroup) + e % kGroup: the mean's index, oja_mean8);
+// get(e): feature e as a float, for the centred kernels.
 template <typename XT>
 struct OjaRow8;
 template <>
 struct OjaRow8<float> {
   static constexpr bool kLo = true;
+  static constexpr int kGroup = 4;
   f32x4 a, b;
   __device__ __forceinline__ void load(const float* p, int k, int d) {
     a = *reinterpret_cast<const f32x4*>(p + min(k, d - 4));
     b = *reinterpret_cast<const f32x4*>(p + min(k + 4, d - 4));
   }
   __device__ __forceinline__ void frags(bf16x8& hi, bf16x8& lo) const { split8(a, b, hi, lo); }
+  __device__ __forceinline__ float get(int e) const { return e < 4 ? a[e] : b[e - 4]; }
 };
 template <>
 struct OjaRow8<OjaBf16> {  // one 16-byte load, already the fragment (d % 8 == 0)
   static constexpr bool kLo = false;
+  static constexpr int kGroup = 8;
   u32x4 a;
   __device__ __forceinline__ void load(const OjaBf16* p, int k, int d) {
     a = *reinterpret_cast<const u32x4*>(p + min(k, d - 8));
   }
   __device__ __forceinline__ void frags(bf16x8& hi, bf16x8&) const { hi = __builtin_bit_cast(bf16x8, a); }
+  __device__ __forceinline__ float get(int e) const { return (e & 1) ? hi_f(a[e >> 1]) : lo_f(a[e >> 1]); }
 };
+template <>
+struct OjaRow8<OjaU8> {  // two 4-byte loads at the float loader's clamps
+  static constexpr bool kLo = false;
+  static constexpr int kGroup = 4;
+  uint32_t a, b;
+  __device__ __forceinline__ void load(const OjaU8* p, int k, int d) {
+    a = *reinterpret_cast<const uint32_t*>(p + min(k, d - 4));
+    b = *reinterpret_cast<const uint32_t*>(p + min(k + 4, d - 4));
+  }
+  __device__ __forceinline__ float get(int e) const { return e < 4 ? oja_byte(a, e) : oja_byte(b, e - 4); }
+  __device__ __forceinline__ void frags(bf16x8& hi, bf16x8&) const {
+    hi = __builtin_bit_cast(bf16x8, u32x4{cvt2(get(0), get(1)), cvt2(get(2), get(3)), cvt2(get(4), get(5)),
+                                          cvt2(get(6), get(7))});
+  }
+};
+// The mean entries of a lane's 8 features at the loader's clamped columns (nothing behind
+// mean[d - 1] is read).
+template <int GROUP>
+__device__ __forceinline__ void oja_mean8(const double* __restrict__ mean, int k, int d, double (&mu)[8]) {
+#pragma unroll
+  for (int g = 0; g < 8 / GROUP; ++g) {
+    const double* m = mean + min(k + GROUP * g, d - GROUP);
+#pragma unroll
+    for (int e = 0; e < GROUP; ++e) mu[GROUP * g + e] = m[e];
+  }
+}
 
 // TN operand: a lane's 4 consecutive features of one row, read back as floats for the
-// [feature][row] transpose region (bf16: one 8-byte load, widened on the way in).
+// [feature][row] transpose region (bf16: one 8-byte load, bytes: one 4-byte load, widened on
+// the way in).
 template <typename XT>
 struct OjaSeg4;
 template <>
@@ -294,11 +339,18 @@ struct OjaSeg4<OjaBf16> {
   __device__ __forceinline__ void load(const OjaBf16* p) { v = *reinterpret_cast<const u32x2*>(p); }
   __device__ __forceinline__ float get(int e) const { return (e & 1) ? hi_f(v[e >> 1]) : lo_f(v[e >> 1]); }
 };
-// The A fragments of 8 transposed values: split for floats; widened bf16 values pack back
-// exactly (round to nearest of a bf16 value is the value).
-template <typename XT>
+template <>
+struct OjaSeg4<OjaU8> {
+  uint32_t v;
+  __device__ __forceinline__ void load(const OjaU8* p) { v = *reinterpret_cast<const uint32_t*>(p); }
+  __device__ __forceinline__ float get(int e) const { return oja_byte(v, e); }
+};
+// The A fragments of 8 transposed values: split where the staged value has a lo piece (float
+// samples, and every centred value); widened bf16 values and bytes pack back exactly (round to
+// nearest of a bf16 value is the value).
+template <bool LO>
 __device__ __forceinline__ void oja_frags8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-  if constexpr (OjaRow8<XT>::kLo) {
+  if constexpr (LO) {
     split8(a, b, hi, lo);
   } else {
     hi = __builtin_bit_cast(bf16x8, u32x4{cvt2(a[0], a[1]), cvt2(a[2], a[3]), cvt2(b[0], b[1]), cvt2(b[2], b[3])});
@@ -324,12 +376,17 @@ constexpr int kOjaPF = 4;  // prefetch depth of the NN / TN passes (k-steps)
 // loads; the 16 rows x 128 B of a wave-instruction pair are whole lines), split to
 // hi / lo in registers; B from the V image (img_kernel), L2-resident.  Loads run
 // PF k-steps ahead of the MFMAs (register ring).  XT = OjaBf16: the lane's 8 features
-// are one 16-byte load that is the fragment itself (OjaRow8), features clamped to d - 8.
-template <int NB, typename XT>
+// are one 16-byte load that is the fragment itself (OjaRow8), features clamped to d - 8;
+// XT = OjaU8: two 4-byte loads, converted to the hi piece.  CEN: the staged value is
+// fl32((double)x - mean[j]) (j the loader's clamped column; the lane's 8 mean entries ride
+// the same register ring), split into hi / lo whatever the sample type - three products.
+template <int NB, typename XT, bool CEN>
 __global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, int64_t ldx, int64_t b,
                                                      int d, int nks, const u32x4* __restrict__ vimg,
-                                                     u32x4* __restrict__ timg) {
+                                                     u32x4* __restrict__ timg,
+                                                     const double* __restrict__ mean) {
   constexpr int PF = kOjaPF;
+  constexpr bool LO = CEN || OjaRow8<XT>::kLo;
   constexpr int KP = 16 * NB;
   __shared__ f32x4 red[8][NB][64];
   __shared__ float tt[16][KP + 1];
@@ -348,9 +405,11 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, i
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   OjaRow8<XT> xs[PF];
+  double mu[CEN ? PF : 1][8];
   u32x4 bh[PF][NB], bl[PF][NB];
   auto load = [&](int ks, int slot) {
     xs[slot].load(xr, 32 * ks + 8 * (lane >> 4), d);
+    if constexpr (CEN) oja_mean8<OjaRow8<XT>::kGroup>(mean, 32 * ks + 8 * (lane >> 4), d, mu[slot]);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bh[slot][nb] = vimg[img_index(ks, nb, 0, lane, NB)];
@@ -359,12 +418,19 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, i
   };
   auto step = [&](int u) {
     bf16x8 ahi, alo;
-    xs[u].frags(ahi, alo);
+    if constexpr (CEN) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = oja_centre(xs[u].get(e), mu[u][e]);
+      split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, ahi, alo);
+    } else {
+      xs[u].frags(ahi, alo);
+    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
       const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
-      acc[nb] = oja_mfma<OjaRow8<XT>::kLo>(ahi, alo, bhi, blo, acc[nb]);
+      acc[nb] = oja_mfma<LO>(ahi, alo, bhi, blo, acc[nb]);
     }
   };
 #pragma unroll
@@ -428,12 +494,17 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, i
 // segment of the block is 32 B), widened on the way into the same LDS region, so the
 // region, the reads and every sum are the float kernel's; the blocks of one 128-B line
 // (4 instead of 2) are consecutive logical blocks, which xcd_logical keeps on one XCD.
-template <int NB, typename XT>
+// XT = OjaU8: 4-byte loads (a row segment of the block is 16 B, 8 blocks a line).  CEN: a
+// lane's 4 features are the same in every k-step, so their 4 mean entries are loaded once,
+// before the loop, at the lane's clamped column; the value is centred on its way into LDS.
+template <int NB, typename XT, bool CEN>
 __global__ __launch_bounds__(512) void oja_tn_kernel(const XT* __restrict__ X, int64_t ldx, int64_t b,
                                                      int d, int nkr, const u32x4* __restrict__ timg,
                                                      float c, float* __restrict__ V,
-                                                     u32x4* __restrict__ vimg) {
+                                                     u32x4* __restrict__ vimg,
+                                                     const double* __restrict__ mean) {
   constexpr int TS = 36;
+  constexpr bool LO = CEN || OjaRow8<XT>::kLo;
   constexpr int KP = 16 * NB;
   __shared__ __attribute__((aligned(16))) float tr[8][16 * TS];
   __shared__ f32x4 red[8][NB][64];
@@ -447,6 +518,11 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const XT* __restrict__ X, i
   // unpredicated loads (see oja_nn_kernel): features >= d and rows >= b read clamped
   // in-range addresses; their products are dropped (f >= d) or meet zero T rows
   const XT* xb_ = X + min(f0 + fl, d - 4);
+  double mu[4] = {0.0, 0.0, 0.0, 0.0};
+  if constexpr (CEN) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) mu[e] = mean[min(f0 + fl, d - 4) + e];
+  }
   const int NKS = nkr;
   const int per = (nkr + 7) / 8;
   const int ks0 = wave * per, ks1 = min(nkr, ks0 + per);
@@ -473,18 +549,18 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const XT* __restrict__ X, i
   auto step = [&](int u) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      T[(fl + e) * TS + rr] = xa[u].get(e);
-      T[(fl + e) * TS + rr + 16] = xb[u].get(e);
+      T[(fl + e) * TS + rr] = CEN ? oja_centre(xa[u].get(e), mu[e]) : xa[u].get(e);
+      T[(fl + e) * TS + rr + 16] = CEN ? oja_centre(xb[u].get(e), mu[e]) : xb[u].get(e);
     }
     const f32x4 a0 = *reinterpret_cast<const f32x4*>(T + (lane & 15) * TS + 8 * (lane >> 4));
     const f32x4 a1 = *reinterpret_cast<const f32x4*>(T + (lane & 15) * TS + 8 * (lane >> 4) + 4);
     bf16x8 ahi, alo;
-    oja_frags8<XT>(a0, a1, ahi, alo);
+    oja_frags8<LO>(a0, a1, ahi, alo);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const bf16x8 bhi = __builtin_bit_cast(bf16x8, bh[u][nb]);
       const bf16x8 blo = __builtin_bit_cast(bf16x8, bl[u][nb]);
-      acc[nb] = oja_mfma<OjaRow8<XT>::kLo>(ahi, alo, bhi, blo, acc[nb]);
+      acc[nb] = oja_mfma<LO>(ahi, alo, bhi, blo, acc[nb]);
     }
   };
 #pragma unroll
@@ -1064,13 +1140,34 @@ hipError_t launch_oja_blk(int nks, const OjaBlk& a, hipStream_t st) {
   }
 }
 
-// The body of both entry points (arguments checked by the caller).  XT = OjaBf16 runs
-// the two-pass kernels only: it never asks for the CU count or the occupancy, never
-// launches the resident kernel, and so never sets the timeout word it clears.
+// The two passes of one batch: T = Xb V (as the TN pass's operand image, every row of its
+// nkr k-steps written, zeros past b), then V += c Xb^T T (and V's image).  false: kp > 64.
+template <typename XT, bool CEN>
+bool launch_oja_passes(int NB, const XT* Xb, int64_t ldx, int64_t b, int64_t d, int nks, int nkr,
+                       const double* mean, float c, float* V, const OjaWs& o, hipStream_t st) {
+  switch (NB) {
+#define DEIG_OJA_NB(x)                                                                             \
+  case x:                                                                                          \
+    hipLaunchKernelGGL((oja_nn_kernel<x, XT, CEN>), dim3((unsigned)(2 * nkr)), dim3(512), 0, st, Xb, \
+                       ldx, b, (int)d, nks, o.vimg, o.timg, mean);                                 \
+    hipLaunchKernelGGL((oja_tn_kernel<x, XT, CEN>), dim3((unsigned)cdiv(d, 16)), dim3(512), 0, st,  \
+                       Xb, ldx, b, (int)d, nkr, o.timg, c, V, o.vimg, mean);                       \
+    return true;
+    DEIG_OJA_NB(1) DEIG_OJA_NB(2) DEIG_OJA_NB(3) DEIG_OJA_NB(4)
+#undef DEIG_OJA_NB
+    default:
+      return false;
+  }
+}
+
+// The body of every entry point (arguments checked by the caller).  XT = OjaBf16 / OjaU8 and
+// every centred call (mean != nullptr: d doubles on the device) run the two-pass kernels
+// only: they never ask for the CU count or the occupancy, never launch the resident kernel,
+// and so never set the timeout word they clear.
 template <typename XT>
-int oja_steps_run(const XT* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta, float* V,
-                  int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes, hipStream_t st,
-                  int algo) {
+int oja_steps_run(const XT* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, const double* mean,
+                  float eta, float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
+                  hipStream_t st, int algo) {
   constexpr bool kF32 = std::is_same<XT, float>::value;
   const int kp = (int)cdiv(k, 16) * 16;
   size_t total = 0;
@@ -1078,7 +1175,7 @@ int oja_steps_run(const XT* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, fl
   if (!ws || total > ws_bytes)
     return fail(DEIG_EWORKSPACE, "oja: workspace %zu < %zu", ws_bytes, total);
   bool blk = false;
-  if constexpr (kF32) blk = algo != DEIG_OJA_TWO_PASS && oja_blk_eligible(b, d, ldx, kp);
+  if constexpr (kF32) blk = !mean && algo != DEIG_OJA_TWO_PASS && oja_blk_eligible(b, d, ldx, kp);
   if (algo == DEIG_OJA_RESIDENT && !blk)
     return fail(DEIG_EINVAL, "oja: the resident path needs b = 4096, d = 512 c <= 3072, k <= 32 "
                              "and %d CUs (got b %lld, d %lld, k %d)", OB_G, (long long)b, (long long)d, k);
@@ -1140,21 +1237,10 @@ int oja_steps_run(const XT* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, fl
     if (!blk) {
       for (int64_t i = i0; i < i1; ++i) {
         const XT* Xb = X + i * b * ldx;
-        // T = Xb V (as the TN pass's operand image, every row of its nkr k-steps
-        // written, zeros past b), then V += eta/b Xb^T T (and V's image)
-        switch (NB) {
-#define DEIG_OJA_NB(x)                                                                           \
-  case x:                                                                                        \
-    hipLaunchKernelGGL((oja_nn_kernel<x, XT>), dim3((unsigned)(2 * nkr)), dim3(512), 0, st, Xb, ldx, \
-                       b, (int)d, nks, o.vimg, o.timg);                                          \
-    hipLaunchKernelGGL((oja_tn_kernel<x, XT>), dim3((unsigned)cdiv(d, 16)), dim3(512), 0, st, Xb, \
-                       ldx, b, (int)d, nkr, o.timg, eta / (float)b, cur, o.vimg);                \
-    break;
-          DEIG_OJA_NB(1) DEIG_OJA_NB(2) DEIG_OJA_NB(3) DEIG_OJA_NB(4)
-#undef DEIG_OJA_NB
-          default:
-            return fail(DEIG_EINVAL, "oja: k = %d > 64", k);
-        }
+        const float c = eta / (float)b;
+        const bool ok = mean ? launch_oja_passes<XT, true>(NB, Xb, ldx, b, d, nks, nkr, mean, c, cur, o, st)
+                             : launch_oja_passes<XT, false>(NB, Xb, ldx, b, d, nks, nkr, nullptr, c, cur, o, st);
+        if (!ok) return fail(DEIG_EINVAL, "oja: k = %d > 64", k);
         DEIG_HIP_CHECK(hipGetLastError());
       }
     }
@@ -1181,7 +1267,7 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
   DEIG_REQUIRE(orth_every >= 1, "oja: orth_every must be >= 1");
   DEIG_REQUIRE(algo == DEIG_OJA_AUTO || algo == DEIG_OJA_TWO_PASS || algo == DEIG_OJA_RESIDENT,
                "oja: unknown algo %d", algo);
-  return oja_steps_run(X, nb, b, d, ldx, eta, V, k, ldv, orth_every, ws, ws_bytes, st, algo);
+  return oja_steps_run(X, nb, b, d, ldx, nullptr, eta, V, k, ldv, orth_every, ws, ws_bytes, st, algo);
 }
 
 // bf16 samples as they are (include/deig.h deig_oja_steps_bf16): the two-pass kernels'
@@ -1203,8 +1289,45 @@ int oja_steps_bf16_launch(const void* X, int64_t nb, int64_t b, int64_t d, int64
   DEIG_REQUIRE(aligned16(X), "oja_bf16: X must be 16-byte aligned");
   DEIG_REQUIRE(reinterpret_cast<uintptr_t>(V) % sizeof(float) == 0,
                "oja_bf16: V must be aligned to its element size");
-  return oja_steps_run(static_cast<const OjaBf16*>(X), nb, b, d, ldx, eta, V, k, ldv, orth_every, ws,
-                       ws_bytes, st, DEIG_OJA_TWO_PASS);
+  return oja_steps_run(static_cast<const OjaBf16*>(X), nb, b, d, ldx, nullptr, eta, V, k, ldv,
+                       orth_every, ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
+}
+
+// Samples of type xtype about a centre (include/deig.h deig_oja_steps_centered): the two-pass
+// kernels' centred instantiations (center == NULL: the uncentred ones), per-type shape rules
+// those of the uncentred entry points and of deig_syrk_u8 (raw).
+int oja_steps_centered_launch(const void* X, int xtype, int64_t nb, int64_t b, int64_t d, int64_t ldx,
+                              const double* center, float eta, float* V, int k, int64_t ldv,
+                              int orth_every, void* ws, size_t ws_bytes, hipStream_t st) {
+  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_BF16 || xtype == DEIG_U8,
+               "oja_centered: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got %d)", xtype);
+  const int q = xtype == DEIG_BF16 ? 8 : 4;  // elements of the narrowest load group
+  const size_t xalign = xtype == DEIG_U8 ? 4 : 16;
+  DEIG_REQUIRE(nb >= 1, "oja_centered: nb must be >= 1 (got %lld)", (long long)nb);
+  DEIG_REQUIRE(b >= 1, "oja_centered: b must be >= 1 (got %lld)", (long long)b);
+  DEIG_REQUIRE(d >= q && d % q == 0, "oja_centered: d must be a multiple of %d, at least %d (got %lld)", q,
+               q, (long long)d);
+  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "oja_centered: need 1 <= k <= min(64, d) (got k=%d, d=%lld)",
+               k, (long long)d);
+  DEIG_REQUIRE(ldx >= d, "oja_centered: ldx must be >= d");
+  DEIG_REQUIRE(ldx % q == 0, "oja_centered: ldx must be a multiple of %d elements", q);
+  DEIG_REQUIRE(ldv >= d, "oja_centered: ldv must be >= d");
+  DEIG_REQUIRE(orth_every >= 1, "oja_centered: orth_every must be >= 1 (got %d)", orth_every);
+  DEIG_REQUIRE(X && V, "oja_centered: X and V must not be NULL");
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(X) % xalign == 0, "oja_centered: X must be %zu-byte aligned",
+               xalign);
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(V) % sizeof(float) == 0,
+               "oja_centered: V must be aligned to its element size");
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % sizeof(double) == 0,
+               "oja_centered: center must be aligned to its element size");
+  if (xtype == DEIG_F32)
+    return oja_steps_run(static_cast<const float*>(X), nb, b, d, ldx, center, eta, V, k, ldv, orth_every,
+                         ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
+  if (xtype == DEIG_BF16)
+    return oja_steps_run(static_cast<const OjaBf16*>(X), nb, b, d, ldx, center, eta, V, k, ldv,
+                         orth_every, ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
+  return oja_steps_run(static_cast<const OjaU8*>(X), nb, b, d, ldx, center, eta, V, k, ldv, orth_every,
+                       ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
 }
 
 // The timeout word of the last oja_steps_launch on this workspace (set by a resident

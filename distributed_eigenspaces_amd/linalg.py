@@ -900,14 +900,20 @@ def projector_distance(A: torch.Tensor, B: torch.Tensor) -> float:
 
 
 # ---------------------------------------------------------------- Oja
-def oja_step(Xb: torch.Tensor, V: torch.Tensor, eta: float) -> torch.Tensor:
+def oja_step(Xb: torch.Tensor, V: torch.Tensor, eta: float, center=None) -> torch.Tensor:
     """In-place mini-batch Oja update V <- orth(V + eta/b Xb^T Xb V) (config 4).
 
     Not in the reference (parity unpinned).  V: (d, k) column-major float32
     (as returned by topk_eigh), k <= 64.  Returns V.  A bfloat16 Xb is consumed as
     bfloat16 under the rules of ``oja_steps`` (no float32 copy, and the call stays
-    asynchronous: that route cannot time out).
+    asynchronous: that route cannot time out); so is a uint8 Xb, and ``center`` (a (d,)
+    float64 tensor: the step is taken on ``Xb - center``) works as it does there.
     """
+    if center is not None:
+        return _oja_steps_centered(Xb, V, eta, None, 1, center, "oja_step", "Xb")
+    xb8 = _oja_u8_samples(Xb, V, "auto", Xb.shape[0] if isinstance(Xb, torch.Tensor) else 0, "oja_step")
+    if xb8 is not None:
+        return _oja_steps_centered(xb8, V, eta, None, 1, None, "oja_step", "Xb")
     xb16 = _oja_bf16_samples(Xb, "auto", "oja_step")
     if xb16 is not None:
         return _oja_steps_bf16(xb16, V, eta, xb16.shape[0], 1, 1, "Xb")
@@ -958,6 +964,91 @@ def _oja_steps_bf16(X: torch.Tensor, V: torch.Tensor, eta: float, b: int, nb: in
     return V
 
 
+# dtype -> (element-type code, elements of the narrowest load group, base alignment in bytes)
+# of the samples deig_oja_steps_centered reads in place
+_OJA_XTYPES = {torch.float32: ("DEIG_F32", 4, 16), torch.bfloat16: ("DEIG_BF16", 8, 16),
+               torch.uint8: ("DEIG_U8", 4, 4)}
+
+
+def _oja_in_place(X: torch.Tensor) -> bool:
+    """Can deig_oja_steps_centered read the 2-D float32 / bfloat16 / uint8 X where it lies?"""
+    _, q, align = _OJA_XTYPES[X.dtype]
+    d = X.shape[1]
+    ldx = _ld(X, 0, d)
+    return (d >= q and d % q == 0 and X.stride(1) == 1 and ldx >= d and ldx % q == 0
+            and X.data_ptr() % align == 0)
+
+
+def _oja_u8_samples(X, V, algo: str, batch: int, name: str) -> torch.Tensor | None:
+    """The uint8 samples of an uncentred Oja call as deig_oja_steps_centered reads them in
+    place, or None when the call keeps the float32 route: not uint8, ``algo="resident"``, a
+    view the entry point cannot read in place, or ``algo="auto"`` at the resident-eligible
+    shape (whose bits are the resident kernel's, not the two-pass kernels')."""
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.uint8 or algo not in ("auto", "two_pass"):
+        return None
+    if X.dim() != 2 or X.shape[0] < 1 or not isinstance(V, torch.Tensor) or V.dim() != 2:
+        return None
+    d = X.shape[1]
+    if algo == "auto" and batch == 4096 and d % 512 == 0 and 0 < d <= 3072 and V.shape[1] <= 32:
+        return None
+    if X.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
+        X = X.to(torch.device("cuda", torch.cuda.current_device()))
+    return X if _oja_in_place(X) else None
+
+
+def _oja_steps_centered(X, V: torch.Tensor, eta: float, batch, orth_every: int, center, name: str,
+                        xname: str) -> torch.Tensor:
+    """Batches of ``batch`` rows (None: all of X is one batch) through
+    deig_oja_steps_centered: uint8 and bfloat16 samples stay what they are, anything else
+    becomes float32; a view the entry point cannot read in place is copied into a
+    zero-padded tensor of the SAME dtype (with ``center`` and V zero-padded to its columns:
+    a padded column stages fl32(0 - 0) = 0 and its row of V stays zero).  No ``oja_check``:
+    the route cannot time out, and the call stays asynchronous."""
+    if isinstance(X, torch.Tensor) and X.dtype in (torch.uint8, torch.bfloat16):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
+        if X.device.type != "cuda":
+            X = X.to(torch.device("cuda", torch.cuda.current_device()))
+    else:
+        X = require_device_tensor(X, name)
+    if X.dim() != 2:
+        raise ValueError(f"{xname} must be 2-D, got shape {tuple(X.shape)}")
+    n, d = X.shape
+    b = n if batch is None else int(batch)
+    nb = n // b if b > 0 else 0
+    if nb < 1:
+        raise ValueError(f"need at least one full batch of {batch} rows, got {n} rows")
+    code, q, _ = _OJA_XTYPES[X.dtype]
+    dp = (d + q - 1) // q * q
+    if not _oja_in_place(X):
+        Xp = torch.zeros((n, dp), dtype=X.dtype, device=X.device)
+        Xp[:, :d] = X
+        X = Xp
+    c = None
+    if center is not None:
+        c = torch.as_tensor(center).to(device=X.device, dtype=torch.float64).reshape(-1)
+        if c.numel() != d:
+            raise ValueError(f"center must have d = {d} entries, got {c.numel()}")
+        if dp != d:
+            c = torch.cat([c, c.new_zeros(dp - d)])
+        elif c.stride(0) != 1 or c.data_ptr() % 8:
+            c = c.clone()
+    Vc = V
+    if dp != d and isinstance(V, torch.Tensor) and V.dim() == 2 and V.shape[0] == d:
+        Vc = torch.zeros((V.shape[1], dp), dtype=V.dtype, device=V.device).t()
+        Vc[:d] = V
+    k = _oja_basis(Vc, X, xname)
+    _call(X.device, "deig_oja_steps_centered",
+          (X.data_ptr(), getattr(_lib, code), nb, b, dp, _ld(X, 0, dp), _ptr(c), eta, Vc.data_ptr(), k,
+           _ld(Vc, 1, dp), int(orth_every)),
+          "deig_oja_workspace", (b, dp, k))
+    if Vc is not V:
+        V.copy_(Vc[:d])
+    return V
+
+
 def oja_check(device, b: int, d: int, k: int) -> None:
     """Raise ``DeigTimeoutError`` if the last Oja call on this thread's workspace for
     (b, d, k) on ``device`` timed out in a resident hand-off (its basis is NaN);
@@ -971,7 +1062,7 @@ def oja_check(device, b: int, d: int, k: int) -> None:
 
 
 def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
-              orth_every: int = 8, algo: str = "auto", check: bool = True) -> torch.Tensor:
+              orth_every: int = 8, algo: str = "auto", check: bool = True, center=None) -> torch.Tensor:
     """In-place Oja over the consecutive row batches X[i*batch:(i+1)*batch] (config 4).
 
     One C call for all batches (no host work in between); the basis is
@@ -998,8 +1089,47 @@ def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
     k = 32, 64 batches, orth_every 8) they took 31.6 us per batch against 40.1 us for
     widening plus the resident kernel and 50.0 us for widening plus the float32 two-pass
     kernels, and at 4096 x 8192, k = 64, 84.8 against 140.1 us (profiles/oja_bf16.json,
-    tools/oja_bf16_bench.py)."""
+    tools/oja_bf16_bench.py).
+
+    ``center``: a (d,) float64 tensor (other dtypes and devices are converted), for
+    example ``PCA.mean_``: the steps are taken on ``X - center``.  Every dtype then goes
+    through include/deig.h deig_oja_steps_centered: each sample is centred where the
+    kernels stage it, ``fl32(float64(x) - center)`` with one rounding, and the result has
+    the bits of ``algo="two_pass"`` on the float32 tensor ``(X.double() - center).float()``
+    without that tensor.  uint8, bfloat16 and float32 samples (anything else becomes
+    float32) are read in place under their layout rules - unit column stride, d and the row
+    stride % 4 == 0 (bfloat16: % 8), a 16-byte (uint8: 4-byte) aligned base; any other view
+    is copied into a zero-padded tensor of the same dtype, never a float32 one.  There is no
+    resident centred kernel: ``algo="resident"`` with a centre is a ValueError, and the
+    call makes no ``oja_check`` and stays asynchronous whatever ``check`` says.
+
+    uint8 samples without a centre are read in place as bytes too (a byte is exact in
+    bfloat16: two products per fragment pair, the bits of ``algo="two_pass"`` on
+    ``X.float()``) for "two_pass", and for "auto" except at the resident-eligible shape
+    (batch 4096, d % 512 == 0, d <= 3072, k <= 32), where the samples are widened and the
+    library chooses, as before: no existing call changes its bits.
+
+    Measured per batch, CholQR included (profiles/oja_centered.json,
+    tools/oja_centered_bench.py): the centred call in place took 39.3 /
+    34.8 / 34.4 us (float32 / bfloat16 / uint8) at config 4's shape against 144 to 146 us
+    for materialising ``(X.double() - center).float()`` and running float32 two-pass, and
+    132.6 / 94.8 / 95.4 against 388 to 396 us at 4096 x 8192, k = 64 - the in-place float32
+    call is faster than materialising too.  Centring costs 10 to 13 % over the uncentred
+    bfloat16 / uint8 kernels (34.8 against 31.6 us, 34.4 against 30.5 us): the third
+    product, the double subtraction and the mean loads together, which the run does not
+    separate.  uint8 bytes in place without a centre: 30.5 us against 59.0 us for widening
+    plus "auto" at config 4's shape, 84.9 against 185.8 us at 4096 x 8192."""
     b = int(batch)
+    if center is not None:
+        if algo not in _lib.OJA_ALGOS:
+            raise ValueError(f"algo must be one of {sorted(_lib.OJA_ALGOS)}, got {algo!r}")
+        if algo == "resident":
+            raise ValueError("oja_steps: there is no centred resident kernel; use algo='auto' or "
+                             "'two_pass' with a center")
+        return _oja_steps_centered(X, V, eta, b, orth_every, center, "oja_steps", "X")
+    x8 = _oja_u8_samples(X, V, algo, b, "oja_steps")
+    if x8 is not None and 0 < b <= x8.shape[0]:
+        return _oja_steps_centered(x8, V, eta, b, orth_every, None, "oja_steps", "X")
     x16 = _oja_bf16_samples(X, algo, "oja_steps")
     if x16 is not None and 0 < b <= x16.shape[0]:
         return _oja_steps_bf16(x16, V, eta, b, x16.shape[0] // b, orth_every, "X")

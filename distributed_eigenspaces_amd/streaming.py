@@ -47,6 +47,13 @@ def broadcast_basis(Vt: torch.Tensor, src: int, group=None) -> torch.Tensor:
     return Vt
 
 
+def _gpu_sums(X: torch.Tensor) -> torch.Tensor:
+    """Float64 column sums of a batch on the device (uint8: the exact integer sums)."""
+    if X.dtype == torch.uint8:
+        return linalg.column_sums_u8(X, "raw")
+    return linalg.column_sums(X)
+
+
 def _gpu_server(Wt: torch.Tensor, k: int, scale: float, q0: torch.Tensor) -> torch.Tensor:
     return linalg.projavg_topk(Wt, k, scale, q0=q0).V
 
@@ -69,11 +76,24 @@ class StreamingOja:
     the aggregation.  bfloat16 batches are consumed as bfloat16 (``linalg.oja_steps``:
     no float32 copy of a batch or a block; the bits of the same calls on
     ``batch.float()``).
+
+    ``center``: None (no centring), a (d,) tensor (a fixed centre, for example
+    ``PCA.mean_``) or ``"running"``: the mean of every row this estimator has been given so
+    far, updated BEFORE the step from the rows of the current ``partial_fit`` batch or the
+    current ``partial_fit_block`` segment.  The running mean is kept as float64 column sums
+    (``sums_fn``: ``linalg.column_sums`` / ``column_sums_u8``, injectable like ``step_fn``)
+    plus a row count; ``aggregate()`` all-reduces both in float64 and every rank keeps
+    ``others = pooled - local`` until the next aggregation, so the centre is
+    ``(local + others) / (n_local + n_others)`` and nothing is counted twice.  With a
+    centre, ``step_fn`` and ``block_fn`` receive it as the keyword ``center=`` (float64,
+    uint8 and bfloat16 batches read in place: ``linalg.oja_steps``); without one they are
+    called as before.  ``mean_`` is the current centre (None without centring, or before
+    the first row of a running mean).
     """
 
     def __init__(self, V0: torch.Tensor, eta: float, agg_every: int = 64, server_rank: int = 0,
                  group=None, step_fn=None, server_fn=None, block_fn=None,
-                 aggregate: str = "projector"):
+                 aggregate: str = "projector", center=None, sums_fn=None):
         if aggregate not in AGGREGATES:
             raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
         self.aggregator = aggregate
@@ -91,10 +111,42 @@ class StreamingOja:
         self.block_fn = block_fn or linalg.oja_steps
         self.batches_seen = 0
         self.aggregations = 0
+        self.sums_fn = sums_fn or _gpu_sums
+        self.running = isinstance(center, str)
+        if self.running and center != "running":
+            raise ValueError(f"center must be None, a (d,) tensor or 'running', got {center!r}")
+        self._fixed = None
+        if center is not None and not self.running:
+            self._fixed = torch.as_tensor(center).to(device=V0.device, dtype=torch.float64).reshape(-1)
+            if self._fixed.numel() != d:
+                raise ValueError(f"center must have d = {d} entries, got {self._fixed.numel()}")
+        # running mean: this rank's rows since the start, the other ranks' as of the last
+        # aggregation (float64 column sums and row counts)
+        self._sums = torch.zeros(d, dtype=torch.float64, device=V0.device)
+        self._rows = 0
+        self._other_sums = torch.zeros(d, dtype=torch.float64, device=V0.device)
+        self._other_rows = 0
+
+    @property
+    def mean_(self):
+        """The current centre: (d,) float64, or None (no centring; no row seen yet)."""
+        if not self.running:
+            return self._fixed
+        n = self._rows + self._other_rows
+        return (self._sums + self._other_sums) / n if n > 0 else None
+
+    def _center_kw(self, X: torch.Tensor) -> dict:
+        """The ``center=`` keyword of the step on the rows X (none without centring); a
+        running mean takes the rows in first."""
+        if self.running:
+            self._sums += self.sums_fn(X).to(device=self._sums.device, dtype=torch.float64)
+            self._rows += int(X.shape[0])
+        c = self.mean_
+        return {} if c is None else {"center": c}
 
     def partial_fit(self, Xb: torch.Tensor) -> torch.Tensor:
         """One Oja step on a row batch; aggregates every ``agg_every`` batches."""
-        self.step_fn(Xb, self.V, self.eta)
+        self.step_fn(Xb, self.V, self.eta, **self._center_kw(Xb))
         self.batches_seen += 1
         if self.agg_every > 0 and self.batches_seen % self.agg_every == 0:
             self.aggregate()
@@ -110,7 +162,8 @@ class StreamingOja:
             seg = nb - i
             if self.agg_every > 0:
                 seg = min(seg, self.agg_every - self.batches_seen % self.agg_every)
-            self.block_fn(X[i * batch:(i + seg) * batch], self.V, self.eta, batch, orth_every)
+            Xs = X[i * batch:(i + seg) * batch]
+            self.block_fn(Xs, self.V, self.eta, batch, orth_every, **self._center_kw(Xs))
             self.batches_seen += seg
             i += seg
             if self.agg_every > 0 and self.batches_seen % self.agg_every == 0:
@@ -127,5 +180,14 @@ class StreamingOja:
             vbar = self.server_fn(Wt, self.k, 1.0 / world, self.V)
             Vt.copy_(vbar.t())
         broadcast_basis(Vt, self.server_rank, self.group)
+        if self.running and world > 1:
+            # pooled (sums, count) in float64; what is not this rank's own is the others'
+            pooled = torch.cat([self._sums, self._sums.new_tensor([float(self._rows)])])
+            buf = comm_tensor(pooled, self.group)
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
+            if buf is not pooled:
+                pooled.copy_(buf)
+            self._other_sums = pooled[:-1] - self._sums
+            self._other_rows = int(round(float(pooled[-1]))) - self._rows
         self.aggregations += 1
         return self.V

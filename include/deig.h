@@ -47,6 +47,9 @@ extern "C" {
  * bits of the fp32 value, as torch.bfloat16 and __bf16 store it; alignment 2 bytes.  Widening
  * is exact, so these entry points return the bits they return for the fp32 copy. */
 #define DEIG_BF16 2
+/* Raw bytes (uint8), one feature per byte: element type of deig_oja_steps_centered only (the
+ * one-shot uint8 entry points take their own DEIG_U8_* modes); alignment 4 bytes. */
+#define DEIG_U8 3
 
 /* Library version, e.g. 0x000400 for 0.4.0.  A caller built against an older header
  * should compare it with the version it was built for before binding entry points
@@ -553,6 +556,36 @@ int deig_oja_error(const void* ws, size_t ws_bytes, int64_t b, int64_t d, int k,
 int deig_oja_steps_bf16(const void* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
                         float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
                         void* stream);
+
+/* Oja steps about a centre, on fp32, bf16 or uint8 samples taken as they are: every sample
+ * is staged as t = fl32((double)x - center[j]), formed in double and rounded once (what the
+ * staging step of deig_pca_transform_* does), then split into hi / lo bf16 pieces - a
+ * centred value has a lo piece whatever the sample type, so every centred call runs three
+ * MFMAs per fragment pair.  center == NULL means no centring: fp32 samples then run the
+ * two-pass kernels, bf16 samples are deig_oja_steps_bf16, and a byte, exact in bf16, is its
+ * own hi piece (two MFMAs, X read at 1 byte an element).
+ * X: (nb*b) x d row-major of element type xtype, row stride ldx elements (DEIG_U8: bytes),
+ * ldx >= d:
+ *   DEIG_F32:  16-byte aligned, d % 4 == 0, d >= 4, ldx % 4 == 0 (deig_oja_steps_f32);
+ *   DEIG_BF16: 16-byte aligned, d % 8 == 0, d >= 8, ldx % 8 == 0 (deig_oja_steps_bf16);
+ *   DEIG_U8:   4-byte aligned,  d % 4 == 0, d >= 4, ldx % 4 == 0 (deig_syrk_u8, raw);
+ * DEIG_F64 or any other xtype is DEIG_EINVAL.  No element behind column d of a row is read.
+ * center: d doubles on the device, in units of x, or NULL; nothing behind center[d - 1] is
+ * read.  V, k, ldv, orth_every as for deig_oja_steps_f32: 1 <= k <= min(64, d), any ldv >= d,
+ * element alignment of V, nothing behind row d of a V column touched.  A single step is
+ * nb = 1, orth_every = 1.
+ * Contract: the result has the bits of deig_oja_steps_ex(T, ..., DEIG_OJA_TWO_PASS, ...) on
+ * the fp32 matrix T[r][j] = fl32((double)x_rj - center_j) (center == NULL: the exact
+ * widening of x).  The resident kernel is never launched, whatever the shape.
+ * Workspace: deig_oja_workspace(b, d, k), the same layout; it may hold anything on entry.
+ * The call clears the workspace's timeout word and never sets it: deig_oja_error on that
+ * workspace returns DEIG_OK.  Asynchronous on `stream`: no allocation, no synchronisation, no
+ * atomics, no wait between workgroups; repeated calls give identical bits.  Argument errors
+ * are DEIG_EINVAL and a short or NULL workspace is DEIG_EWORKSPACE, both before any GPU work.
+ * Additive: probe for the symbol, deig_version() is unchanged. */
+int deig_oja_steps_centered(const void* X, int xtype, int64_t nb, int64_t b, int64_t d,
+                            int64_t ldx, const double* center, float eta, float* V, int k,
+                            int64_t ldv, int orth_every, void* ws, size_t ws_bytes, void* stream);
 
 /* Projection onto an estimated eigenspace: Y = X W.
  * Replaces the notebook's  online_distributed_PCA = lambda X: X @ matrix_w

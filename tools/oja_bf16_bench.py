@@ -76,7 +76,8 @@ def run_shape(b, d, k, nb, orth, steps, warmup, trials, dev):
     x = make_samples(nb * b, d, dev)
     g = torch.Generator(device="cpu").manual_seed(100 + k)
     V0 = torch.linalg.qr(torch.randn(d, k, generator=g, dtype=torch.float64))[0].float().to(dev)
-    Vs = {name: V0.t().contiguous().t() for name in ("a", "b", "c")}  # column-major
+    # a column-major buffer each (V0 is column-major already: V0.t().contiguous() would be V0 itself)
+    Vs = {name: torch.empty((k, d), dtype=torch.float32, device=dev).t() for name in ("a", "b", "c")}
 
     def route(name, widen, algo):
         def fn():
