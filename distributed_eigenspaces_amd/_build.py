@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdeig.so")
 SOURCES = ["capi.hip", "solver.hip", "syrk.hip", "syrk_split.hip", "syrk_u8.hip", "skinny.hip", "rr.hip", "oja.hip",
-           "project.hip", "sweep.hip", "shift.hip", "procrustes.hip", "pca.hip", "pca_u8.hip", "syrk_bf16.hip", "pca_bf16.hip"]
+           "project.hip", "sweep.hip", "shift.hip", "procrustes.hip", "pca.hip", "pca_u8.hip", "syrk_bf16.hip", "pca_bf16.hip", "gram.hip"]
 # Per-source extra flags.  sweep.hip: keep the split's scalar f32 subtractions
 # unpacked (v_pk_add_f32 beside MFMAs costs issue cycles, MI355X_MICROARCH.md).
 # pca_bf16.hip: the super-chunk loop of pca_packed_tile.hpp starts on a 64-byte instruction

@@ -382,6 +382,72 @@ int deig_projavg_topk_f32(const float* Wt, int64_t d, int64_t mk, int64_t ldw, f
                               evals, sweeps_out, resid_out, nullptr, ws, ws_bytes, stream);
 }
 
+size_t deig_gram_apply_workspace(int64_t n, int64_t d, int p, int xtype) {
+  return gram_apply_workspace_bytes(n, d, p, xtype);
+}
+
+int deig_gram_apply(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                    float alpha, const float* Q, int p, int64_t ldq, float* Y, int64_t ldy, void* ws,
+                    size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  return gram_apply_launch(X, xtype, n, d, ldx, center, alpha, Q, p, ldq, Y, ldy, ws, ws_bytes,
+                           (hipStream_t)stream);
+}
+
+// The shape rules of the covariance-free solve that do not involve pointers.
+static bool topk_samples_shape_ok(int64_t n, int64_t d, int k, int p, int xtype) {
+  return gram_apply_workspace_bytes(n, d, 16, xtype) > 0 && k >= 1 && k <= 128 && k <= d && p >= 16 &&
+         p <= 128 && p % 16 == 0 && p >= k && p <= d;
+}
+
+size_t deig_topk_samples_workspace(int64_t n, int64_t d, int k, int p, int xtype,
+                                   const deig_solver_opts* opts) {
+  if (check_opts(opts) || !topk_samples_shape_ok(n, d, k, p, xtype)) return 0;
+  return solver_workspace_bytes(d, k, p, true, 0, make_opts(opts), DEIG_F32, n, xtype);
+}
+
+int deig_topk_samples(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                      float scale, int k, int p, int max_sweeps, float tol, const float* Q0, int k0,
+                      int64_t ldq0, float* V, int64_t ldv, float* evals, int* sweeps_out,
+                      float* resid_out, const deig_solver_opts* opts, void* ws, size_t ws_bytes,
+                      void* stream) {
+  g_err[0] = 0;
+  const char* what = "topk_samples";
+  if (int rc = check_opts(opts)) return rc;
+  if (int rc = gram_apply_check(X, xtype, n, d, ldx, center, what)) return rc;
+  if (k < 1 || k > 128 || k > d)
+    return fail(DEIG_EINVAL, "%s: need 1 <= k <= min(128, d) (k=%d, d=%lld)", what, k, (long long)d);
+  if (p < 16 || p > 128 || p % 16 != 0)
+    return fail(DEIG_EINVAL, "%s: p must be a multiple of 16 in 16..128 (got %d)", what, p);
+  if (p < k || p > d)
+    return fail(DEIG_EINVAL, "%s: the subspace needs k <= p <= d (k=%d, p=%d, d=%lld)", what, k, p,
+                (long long)d);
+  if (max_sweeps < 1) return fail(DEIG_EINVAL, "%s: max_sweeps must be >= 1", what);
+  if (!V || !evals || ldv < d) return fail(DEIG_EINVAL, "%s: V and evals must not be NULL, ldv >= d", what);
+  if (k0 < 0 || k0 > p || (k0 > 0 && (!Q0 || ldq0 < d)))
+    return fail(DEIG_EINVAL, "%s: bad warm start (k0=%d, p=%d)", what, k0, p);
+  const size_t need = deig_topk_samples_workspace(n, d, k, p, xtype, opts);
+  if (!ws || ws_bytes < need)
+    return fail(DEIG_EWORKSPACE, "%s: workspace %zu bytes < required %zu", what, ws ? ws_bytes : (size_t)0,
+                need);
+  SolveProblem pr{};
+  pr.op.implicit = true;
+  pr.op.stype = DEIG_F32;
+  pr.op.X = X;
+  pr.op.xtype = xtype;
+  pr.op.n = n;
+  pr.op.ldx = ldx;
+  pr.op.center = center;
+  pr.op.scale = scale;
+  pr.Q0 = Q0;
+  pr.k0 = k0;
+  pr.ldq0 = ldq0;
+  pr.V = V;
+  pr.evals = evals;
+  return solve_lockstep(1, &pr, d, k, p, max_sweeps, tol, ldv, sweeps_out, resid_out, nullptr,
+                        make_opts(opts), ws, ws_bytes, (hipStream_t)stream);
+}
+
 size_t deig_procrustes_workspace(int64_t d, int64_t mk, int k) {
   return procrustes_workspace_bytes(d, mk, k);
 }

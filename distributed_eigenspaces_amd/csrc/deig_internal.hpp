@@ -160,6 +160,23 @@ int skinny_launch(bool trans_a, const float* A, int64_t lda, const float* B, int
                   float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, float alpha,
                   float beta, float* slab, size_t slab_bytes, hipStream_t stream,
                   const ProbBatch* batch = nullptr);
+// Its split-K factor for an M x K problem (does not decrease in K), and the slice-order sum
+// of ks partial slabs part[ks][M][N]: C = alpha sum + beta C.
+int skinny_split_k(int64_t M, int64_t K);
+int skinny_reduce_launch(const float* part, int ks, float* C, int64_t ldc, int64_t M, int N,
+                         float alpha, float beta, hipStream_t stream, const ProbBatch* batch = nullptr);
+
+// The sample operator Y = alpha Xc^T (Xc Q) of the covariance-free solve (gram.hip); xtype
+// DEIG_F32 / DEIG_BF16 / DEIG_U8 (raw bytes), center: d doubles or nullptr, Q and Y d x p
+// row-major.  Runs in row chunks sized by the workspace.
+size_t gram_apply_workspace_bytes(int64_t n, int64_t d, int p, int xtype);
+int64_t gram_recommended_rows(int64_t n, int64_t d, int xtype);
+// the rules for X, n, d, ldx and center alone (`what` names the entry point)
+int gram_apply_check(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                     const char* what);
+int gram_apply_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                      float alpha, const float* Q, int p, int64_t ldq, float* Y, int64_t ldy, void* ws,
+                      size_t ws_bytes, hipStream_t stream);
 
 // bf16x6 symmetric sweep (sweep.hip): Y = alpha * S Q, S symmetric d x d
 // row-major, Q d x p (ldq), Y d x p (ldy), p % 16 == 0, p <= 128.
@@ -277,28 +294,30 @@ int oja_error(const void* ws, size_t ws_bytes, int64_t b, int64_t d, int k, hipS
 size_t project_workspace_bytes(int64_t n, int64_t d, int k);
 int project_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const float* W, int k,
                    int64_t ldw, float* Y, int64_t ldy, void* ws, size_t ws_bytes, hipStream_t st);
-// Wr (d x kp row-major, kp % 16 == 0, columns >= k zero) from the column-major d x k W.
+// Wr (d x kp row-major, kp % 16 == 0, columns >= k zero) from the d x k W: column-major, or
+// with w_rowmajor row-major (row stride ldw >= k) - the three transform launches below alike.
 int pack_w_launch(const float* W, int64_t ldw, int64_t d, int k, int kp, float* Wr,
-                  hipStream_t st);
+                  hipStream_t st, bool w_rowmajor = false);
 
 // Fused centred transform (pca.hip): Y = (X - 1 mean^T) W, row energies and residuals.
 size_t pca_transform_workspace_bytes(int64_t n, int64_t d, int k);
 int pca_transform_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
                          const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
-                         float* energy, void* ws, size_t ws_bytes, hipStream_t st);
+                         float* energy, void* ws, size_t ws_bytes, hipStream_t st,
+                         bool w_rowmajor = false);
 // The same from uint8 samples, centred when the bytes are staged (pca_u8.hip).
 size_t pca_transform_u8_workspace_bytes(int64_t n, int64_t d, int k);
 int pca_transform_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
                             const double* mean, const float* W, int k, int64_t ldw, float* Y,
                             int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
-                            hipStream_t st);
+                            hipStream_t st, bool w_rowmajor = false);
 
 // The same from bf16 samples, widened (exactly) and centred when they are staged (pca_bf16.hip).
 size_t pca_transform_bf16_workspace_bytes(int64_t n, int64_t d, int k);
 int pca_transform_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
                               const float* W, int k, int64_t ldw, float* Y, int64_t ldy,
                               float* resid, float* energy, void* ws, size_t ws_bytes,
-                              hipStream_t st);
+                              hipStream_t st, bool w_rowmajor = false);
 
 // Procrustes-aligned basis average and residual-form subspace distance (procrustes.hip).
 // Both validate their arguments (DEIG_EINVAL) before any GPU work; the workspace
@@ -336,6 +355,13 @@ struct Operator {
   const float* Wt;  // implicit: scale * Wt^T Wt
   int64_t mk, ldw;
   float scale;
+  // implicit, sample form (X != nullptr, Wt unused): scale * Xc^T Xc of the n x d samples X
+  // (xtype DEIG_F32 / DEIG_BF16 / DEIG_U8, row stride ldx) about center (d doubles or
+  // nullptr), applied by gram_apply_launch without forming d x d.  Single solves only.
+  const void* X;
+  int xtype;
+  int64_t n, ldx;
+  const double* center;
   // applied on top of the base operator (explicit S: folded in, in double, by sweep_prepare
   // or into the fp32 sweep's copy of S; implicit: applied as products after each product):
   // + shift I - Vd diag(lamd) Vd^T
@@ -351,8 +377,9 @@ int default_subspace(int64_t d, int k);
 // Then it needs only its element alignment, else 16 bytes and lds % 4 == 0.
 bool solver_stages(int64_t d, int k, int p);
 // Workspace of one problem (mk: rows of an implicit operator's Wt; stype: an explicit S's).
+// gram_n > 0: the sample form of the implicit operator on gram_n rows of type gram_xtype.
 size_t solver_workspace_bytes(int64_t d, int k, int p, bool implicit, int64_t mk, const Opts& o,
-                              int stype);
+                              int stype, int64_t gram_n = 0, int gram_xtype = 0);
 
 // One problem of a solve: its operator, warm start (k0 columns of Q0, column-major,
 // ldq0; k0 = 0: none) and outputs (V d x k column-major, evals ascending).

@@ -127,12 +127,13 @@ size_t pca_transform_workspace_bytes(int64_t n, int64_t d, int k) {
 
 int pca_transform_launch(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
                          const float* W, int k, int64_t ldw, float* Y, int64_t ldy, float* resid,
-                         float* energy, void* ws, size_t ws_bytes, hipStream_t st) {
+                         float* energy, void* ws, size_t ws_bytes, hipStream_t st,
+                         bool w_rowmajor) {
   DEIG_REQUIRE(k >= 1 && k <= 256, "pca_transform: k=%d must be in 1..256", k);
   DEIG_REQUIRE(n >= 1 && d >= 4 && d % 4 == 0, "pca_transform: need n >= 1, d >= 4, d %% 4 == 0");
   DEIG_REQUIRE(ldx >= d, "pca_transform: ldx must be >= d");
   DEIG_REQUIRE(ldx % 4 == 0, "pca_transform: ldx %% 4 == 0 required");
-  DEIG_REQUIRE(ldw >= d, "pca_transform: ldw must be >= d");
+  DEIG_REQUIRE(ldw >= (w_rowmajor ? (int64_t)k : d), "pca_transform: ldw must be >= d");
   DEIG_REQUIRE(Y || resid || energy, "pca_transform: need at least one output (Y, resid, energy)");
   DEIG_REQUIRE(!Y || ldy >= k, "pca_transform: ldy must be >= k");
   DEIG_REQUIRE(X && W && aligned16(X), "pca_transform: X (16-byte aligned) and W must not be NULL");
@@ -142,7 +143,7 @@ int pca_transform_launch(const float* X, int64_t n, int64_t d, int64_t ldx, cons
     return fail(DEIG_EWORKSPACE, "pca_transform: workspace %zu bytes < required %zu", ws_bytes, need);
   const int kp = (int)cdiv(k, 16) * 16;
   float* Wr = static_cast<float*>(ws);
-  if (int rc = pack_w_launch(W, ldw, d, k, kp, Wr, st)) return rc;
+  if (int rc = pack_w_launch(W, ldw, d, k, kp, Wr, st, w_rowmajor)) return rc;
   const dim3 grid((unsigned)cdiv(n, PBM));
   const int rc = tile::dispatch_nb(kp / 16, [&](auto nb) {
     return tile::launch<pca_transform_kernel<nb()>>(grid, tile::shm_bytes(nb() * 16, PAST), st, X,

@@ -37,7 +37,7 @@ size_t pca_transform_bf16_workspace_bytes(int64_t n, int64_t d, int k) {
 int pca_transform_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, const double* mean,
                               const float* W, int k, int64_t ldw, float* Y, int64_t ldy,
                               float* resid, float* energy, void* ws, size_t ws_bytes,
-                              hipStream_t st) {
+                              hipStream_t st, bool w_rowmajor) {
   auto check = [&] {
     DEIG_REQUIRE(n >= 1, "pca_transform_bf16: n must be >= 1 (got %lld)", (long long)n);
     DEIG_REQUIRE(d >= 8 && d % 8 == 0 && d <= (int64_t(1) << 31),
@@ -47,7 +47,8 @@ int pca_transform_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, 
     return (int)DEIG_OK;
   };
   return ptile::launch<Bf16Source>("pca_transform_bf16", static_cast<const uint16_t*>(X), n, d, ldx,
-                                   mean, W, k, ldw, Y, ldy, resid, energy, ws, ws_bytes, st, check);
+                                   mean, W, k, ldw, Y, ldy, resid, energy, ws, ws_bytes, st, check,
+                                   w_rowmajor);
 }
 
 }  // namespace deig

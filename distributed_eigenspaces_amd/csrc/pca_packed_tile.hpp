@@ -274,11 +274,11 @@ template <class Src, class Check>
 int launch(const char* what, const typename Src::Elem* X, int64_t n, int64_t d, int64_t ldx,
            const double* mean, const float* W, int k, int64_t ldw, float* Y, int64_t ldy,
            float* resid, float* energy, void* ws, size_t ws_bytes, hipStream_t st,
-           Check check_shape) {
+           Check check_shape, bool w_rowmajor = false) {
   constexpr int SK = kSuper<Src>;
   DEIG_REQUIRE(k >= 1 && k <= 256, "%s: k=%d must be in 1..256", what, k);
   if (int rc = check_shape()) return rc;
-  DEIG_REQUIRE(ldw >= d, "%s: ldw must be >= d", what);
+  DEIG_REQUIRE(ldw >= (w_rowmajor ? (int64_t)k : d), "%s: ldw must be >= d", what);
   DEIG_REQUIRE(Y || resid || energy, "%s: need at least one output (Y, resid, energy)", what);
   DEIG_REQUIRE(!Y || ldy >= k, "%s: ldy must be >= k", what);
   DEIG_REQUIRE(X && reinterpret_cast<uintptr_t>(X) % Src::kXAlign == 0 && W,
@@ -290,7 +290,7 @@ int launch(const char* what, const typename Src::Elem* X, int64_t n, int64_t d, 
   const int kp = (int)cdiv(k, 16) * 16;
   const int64_t dpad = cdiv(d, SK) * SK;
   float* Wr = static_cast<float*>(ws);
-  if (int rc = pack_w_launch(W, ldw, d, k, kp, Wr, st)) return rc;
+  if (int rc = pack_w_launch(W, ldw, d, k, kp, Wr, st, w_rowmajor)) return rc;
   if (dpad > d)
     DEIG_HIP_CHECK(hipMemsetAsync(Wr + d * kp, 0, sizeof(float) * (size_t)(dpad - d) * kp, st));
   double* mpad = nullptr;

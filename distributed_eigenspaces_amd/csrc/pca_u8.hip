@@ -81,14 +81,14 @@ size_t pca_transform_u8_workspace_bytes(int64_t n, int64_t d, int k) {
 int pca_transform_u8_launch(const uint8_t* X, int64_t n, int64_t d, int64_t ldx, int mode,
                             const double* mean, const float* W, int k, int64_t ldw, float* Y,
                             int64_t ldy, float* resid, float* energy, void* ws, size_t ws_bytes,
-                            hipStream_t st) {
+                            hipStream_t st, bool w_rowmajor) {
   const char* what = "pca_transform_u8";
   auto check = [&] { return u8_check_shape(what, n, d, ldx, mode, int64_t(1) << 31); };
   if (mode == DEIG_U8_RAW)
     return ptile::launch<U8Raw>(what, X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws,
-                                ws_bytes, st, check);
+                                ws_bytes, st, check, w_rowmajor);
   return ptile::launch<U8Gray3>(what, X, n, d, ldx, mean, W, k, ldw, Y, ldy, resid, energy, ws,
-                                ws_bytes, st, check);  // an unknown mode: check's to report
+                                ws_bytes, st, check, w_rowmajor);  // an unknown mode: check's to report
 }
 
 }  // namespace deig

@@ -7,14 +7,15 @@
 namespace deig {
 namespace {
 
-__global__ __launch_bounds__(256) void w_to_rowpad(const float* __restrict__ W, int64_t ldw,
-                                                   int64_t d, int k, int kp,
+// W element (r, j) at W[r * rs + j * cs]: column-major (rs = 1, cs = ldw) or row-major
+__global__ __launch_bounds__(256) void w_to_rowpad(const float* __restrict__ W, int64_t rs,
+                                                   int64_t cs, int64_t d, int k, int kp,
                                                    float* __restrict__ Wr) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= d * kp) return;
   const int64_t r = idx / kp;
   const int j = (int)(idx - r * kp);
-  Wr[idx] = (j < k) ? W[r + (int64_t)j * ldw] : 0.f;
+  Wr[idx] = (j < k) ? W[r * rs + (int64_t)j * cs] : 0.f;
 }
 
 __global__ __launch_bounds__(256) void crop_rows(const float* __restrict__ T, int64_t n, int k,
@@ -44,12 +45,13 @@ ProjWs carve_proj(void* ws, size_t cap, int64_t n, int64_t d, int kp, bool direc
 
 }  // namespace
 
-// Wr (d x kp row-major, columns >= k zero) from the column-major d x k W; also the
-// W image of the fused centred transform (pca.hip).
+// Wr (d x kp row-major, columns >= k zero) from the d x k W, column-major or (w_rowmajor)
+// row-major with leading dimension ldw; also the W image of the fused centred transforms
+// (pca.hip, pca_packed_tile.hpp).
 int pack_w_launch(const float* W, int64_t ldw, int64_t d, int k, int kp, float* Wr,
-                  hipStream_t st) {
-  hipLaunchKernelGGL(w_to_rowpad, dim3((unsigned)cdiv(d * kp, 256)), dim3(256), 0, st, W, ldw, d,
-                     k, kp, Wr);
+                  hipStream_t st, bool w_rowmajor) {
+  hipLaunchKernelGGL(w_to_rowpad, dim3((unsigned)cdiv(d * kp, 256)), dim3(256), 0, st, W,
+                     w_rowmajor ? ldw : int64_t(1), w_rowmajor ? int64_t(1) : ldw, d, k, kp, Wr);
   DEIG_HIP_CHECK(hipGetLastError());
   return DEIG_OK;
 }

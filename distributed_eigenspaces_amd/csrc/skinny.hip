@@ -203,6 +203,22 @@ int choose_ks(int64_t M, int64_t K) {
 
 }  // namespace
 
+int skinny_split_k(int64_t M, int64_t K) { return choose_ks(M, K); }
+
+int skinny_reduce_launch(const float* part, int ks, float* C, int64_t ldc, int64_t M, int N,
+                         float alpha, float beta, hipStream_t stream, const ProbBatch* batch) {
+  const ProbBatch pbt = batch ? *batch : one_problem();
+  const int64_t tot = M * N;
+  if (ldc % 4 == 0 && aligned16(C))
+    hipLaunchKernelGGL(skinny_reduce_kernel<4>, dim3((unsigned)cdiv(tot / 4, 256), (unsigned)pbt.n),
+                       dim3(256), 0, stream, part, ks, C, ldc, M, N, alpha, beta, pbt);
+  else
+    hipLaunchKernelGGL(skinny_reduce_kernel<1>, dim3((unsigned)cdiv(tot, 256), (unsigned)pbt.n),
+                       dim3(256), 0, stream, part, ks, C, ldc, M, N, alpha, beta, pbt);
+  DEIG_HIP_CHECK(hipGetLastError());
+  return DEIG_OK;
+}
+
 size_t skinny_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   const int ks = choose_ks(M, K);
   return ks > 1 ? (size_t)ks * M * N * sizeof(float) : 0;
@@ -233,16 +249,7 @@ int skinny_launch(bool trans_a, const float* A, int64_t lda, const float* B, int
                    : launch_t<false>(NB, A, lda, B, ldb, C, ldc, M, K, alpha, beta, slab, ks,
                                      stream, pbt);
   if (rc) return rc;
-  if (ks > 1) {
-    const int64_t tot = M * N;
-    if (ldc % 4 == 0 && aligned16(C))
-      hipLaunchKernelGGL(skinny_reduce_kernel<4>, dim3((unsigned)cdiv(tot / 4, 256), (unsigned)pbt.n),
-                         dim3(256), 0, stream, slab, ks, C, ldc, M, (int)N, alpha, beta, pbt);
-    else
-      hipLaunchKernelGGL(skinny_reduce_kernel<1>, dim3((unsigned)cdiv(tot, 256), (unsigned)pbt.n),
-                         dim3(256), 0, stream, slab, ks, C, ldc, M, (int)N, alpha, beta, pbt);
-    DEIG_HIP_CHECK(hipGetLastError());
-  }
+  if (ks > 1) return skinny_reduce_launch(slab, ks, C, ldc, M, (int)N, alpha, beta, stream, &pbt);
   return DEIG_OK;
 }
 

@@ -63,15 +63,19 @@ struct SolverWs {
   size_t slab_bytes;
   void* sweep_ws;  // bf16x6 sweep image (explicit S only)
   size_t sweep_bytes;
+  void* gram_ws;  // the sample operator's own workspace (in place of Zt and the Wt slabs)
+  size_t gram_bytes;
   float* Sdef;     // d x d: the shifted / deflated S of the fp32 sweep (explicit S, no image)
 };
 
 // p: the widest block subspace, kb: the most pairs one block targets (<= p), k:
 // all pairs (the implicit operator deflates its locked ones by plain products).
+// gram_bytes > 0: the implicit operator in its sample form (mk == 0).
 SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int64_t mk,
-                      bool image, size_t* total) {
+                      bool image, size_t* total, size_t gram_bytes = 0) {
   Carve c(ws, cap);
   SolverWs w;
+  const bool implicit = mk > 0 || gram_bytes > 0;
   w.rr.Z = c.take<float>((size_t)d * 2 * p);
   w.rr.C = c.take<float>((size_t)4 * p * p);
   w.rr.Linv = c.take<float>((size_t)p * p);
@@ -85,8 +89,8 @@ SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int
   w.rr.info = c.take<int>(16);
   w.Zt = mk > 0 ? c.take<float>((size_t)mk * p) : nullptr;
   w.T = c.take<float>((size_t)d * p);
-  w.Tdef = mk > 0 ? c.take<float>((size_t)k * p) : nullptr;
-  w.rq = mk > 0 ? nullptr : c.take<char>(rq_workspace_bytes(d, k));
+  w.Tdef = implicit ? c.take<float>((size_t)k * p) : nullptr;
+  w.rq = implicit ? nullptr : c.take<char>(rq_workspace_bytes(d, k));
   size_t sb = skinny_workspace_bytes(2 * p, 2 * p, d);  // Gram
   auto need = [&](int64_t M, int64_t N, int64_t K) {
     const size_t b = skinny_workspace_bytes(M, N, K);
@@ -95,10 +99,10 @@ SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int
   if (mk > 0) {
     need(mk, p, d);  // Wt Q
     need(d, p, mk);  // Wt^T Zt
-  } else if (!image) {
+  } else if (!image && !implicit) {
     need(d, p, d);  // S Q
   }
-  if (mk > 0) {  // plain-product deflation of the implicit operator: Vd^T Q and Vd T
+  if (implicit) {  // plain-product deflation of the implicit operator: Vd^T Q and Vd T
     need(k, p, d);
     need(d, p, k);
   }
@@ -110,7 +114,9 @@ SolverWs carve_solver(void* ws, size_t cap, int64_t d, int kb, int k, int p, int
     w.sweep_bytes = sweep_workspace_bytes(d, p);
     w.sweep_ws = c.take<char>(w.sweep_bytes);
   }
-  w.Sdef = (!image && mk == 0) ? c.take<float>((size_t)d * d) : nullptr;
+  w.Sdef = (!image && !implicit) ? c.take<float>((size_t)d * d) : nullptr;
+  w.gram_bytes = gram_bytes;
+  w.gram_ws = gram_bytes ? c.take<char>(gram_bytes) : nullptr;
   *total = c.off;
   return w;
 }
@@ -176,6 +182,9 @@ int apply_op_plain(const Operator& op, const SolverWs& w, int64_t d, int p, hipS
   if (!op.implicit) {
     rc = skinny_launch(true, static_cast<const float*>(op.S), op.lds, Q, ld, Y, ld, d, p, d, 1.f,
                        0.f, w.slab, w.slab_bytes, st);
+  } else if (op.X) {
+    rc = gram_apply_launch(op.X, op.xtype, op.n, d, op.ldx, op.center, op.scale, Q, p, ld, Y, ld,
+                           w.gram_ws, w.gram_bytes, st);
   } else {
     rc = skinny_launch(false, op.Wt, op.ldw, Q, ld, w.Zt, p, op.mk, p, d, 1.f, 0.f, w.slab,
                        w.slab_bytes, st);
@@ -853,7 +862,11 @@ struct SolveSM {
       sv.lam_h = sv.hs->lam;
       sv.res_h = sv.hs->res;
     }
-    sv.w = carve_solver(ws_solver, ws_solver_bytes, d, kb, k, pb0, op.implicit ? op.mk : 0, image, &total);
+    const size_t gram_bytes = (op.implicit && op.X) ? gram_apply_workspace_bytes(op.n, d, pb0, op.xtype) : 0;
+    if (op.implicit && op.X)
+      DEIG_REQUIRE(gram_bytes > 0 && k <= kMaxP, "solver: the sample operator needs 1 <= k <= 128");
+    sv.w = carve_solver(ws_solver, ws_solver_bytes, d, kb, k, pb0, (op.implicit && !op.X) ? op.mk : 0,
+                        image, &total, gram_bytes);
     if (!ws || total > ws_solver_bytes)
       return fail(DEIG_EWORKSPACE, "solver: workspace %zu bytes < required %zu", ws_bytes, total + cs.off);
     op0 = op;
@@ -1332,7 +1345,7 @@ int default_subspace(int64_t d, int k) {
 bool solver_stages(int64_t d, int k, int p) { return solver_dims(d, k, p, false).staged; }
 
 size_t solver_workspace_bytes(int64_t d, int k, int p, bool implicit, int64_t mk, const Opts& o,
-                              int stype) {
+                              int stype, int64_t gram_n, int gram_xtype) {
   if (d < 1 || k < 1) return 0;
   const Dims dm = solver_dims(d, k, p, implicit);
   int pb = dm.pb, kb = dm.kb;
@@ -1342,7 +1355,10 @@ size_t solver_workspace_bytes(int64_t d, int k, int p, bool implicit, int64_t mk
   Carve c(nullptr, 0);
   carve_stage(c, dm, k, stype);
   size_t total = 0;
-  carve_solver(nullptr, 0, dm.dp, kb, k, pb, implicit ? mk : 0, image, &total);
+  const size_t gram_bytes =
+      (implicit && gram_n > 0) ? gram_apply_workspace_bytes(gram_n, dm.dp, pb, gram_xtype) : 0;
+  if (implicit && gram_n > 0 && !gram_bytes) return 0;
+  carve_solver(nullptr, 0, dm.dp, kb, k, pb, (implicit && gram_n <= 0) ? mk : 0, image, &total, gram_bytes);
   return c.off + total;
 }
 

@@ -33,6 +33,18 @@ the workers' covariance is ``linalg.sigma_hat``'s bf16 kernel (one exact MFMA pr
 float32 copy) or, centred, ``linalg.sigma_hat_centered`` reading bf16, and the column sums of
 the pooled mean read bf16 too.
 
+``covariance="free"`` (opt-in; the default ``"explicit"`` is everything above, unchanged) is
+the covariance-free worker route: every logical worker is ``linalg.topk_samples`` on its
+shard - the top-k of X_i^T X_i / n_i straight from the float32, bfloat16 or uint8 (raw bytes)
+rows, about the pooled mean with ``center=True`` - and no d x d covariance is ever formed.
+It is the route for shards with far fewer rows than features and for d beyond the covariance
+kernels; at tall shards it is slower than the explicit route.  Its workers run in the serial
+worker loop: ``batched_workers`` and ``concurrent_workers`` do not apply and are ignored.
+uint8 shards go through as raw bytes, uncentred or with ``center=True, u8_mode="raw"``;
+``u8_mode="gray"`` and float64 samples are not supported by this route.  The operator is
+implicit, so the solver does not deflate a dominant mean direction: uncentred data with a
+large mean should use ``center=True`` or the explicit route.
+
 The collective layer only uses ``torch.distributed`` with tensors on the rank's
 device, so it runs on ``gloo`` with CPU tensors too (multi-process tests); the
 per-worker compute is injectable for those tests and defaults to the GPU ops.
@@ -52,6 +64,7 @@ __all__ = ["shard_ranges", "rank_shards", "EstimatorResult", "DistributedEigensp
 
 
 AGGREGATES = ("projector", "procrustes")
+COVARIANCES = ("explicit", "free")
 
 
 def shard_ranges(n_rows: int, batches_number: int):
@@ -140,13 +153,28 @@ def _gpu_worker(x: torch.Tensor, k: int, center=None, u8_mode=None, **kw):
     return r.V, r.evals, r.sweeps
 
 
+def _gpu_worker_free(x: torch.Tensor, k: int, center=None, u8_mode=None, **kw):
+    """The covariance-free worker: top-k straight from the shard's rows (uint8: raw bytes)."""
+    r = linalg.topk_samples(x, k, center=center, **kw)
+    return r.V, r.evals, r.sweeps
+
+
 class DistributedEigenspaceEstimator:
     def __init__(self, k: int, workers_per_rank: int = 1, server_rank: int = 0, group=None,
                  worker_fn=None, solver_kw=None, concurrent_workers: bool = False,
                  batched_workers: bool = True, aggregate: str = "projector",
-                 center: bool = False, u8_mode: str | None = None):
+                 center: bool = False, u8_mode: str | None = None, covariance: str = "explicit"):
         if aggregate not in AGGREGATES:
             raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+        if covariance not in COVARIANCES:
+            raise ValueError(f"covariance must be one of {COVARIANCES}, got {covariance!r}")
+        if covariance == "free" and u8_mode == "gray":
+            raise ValueError("covariance='free' reads uint8 samples as raw bytes only: "
+                             "u8_mode='gray' needs covariance='explicit'")
+        # "explicit" (default): sigma_hat* + topk_eigh per worker; "free": linalg.topk_samples
+        # on the shard's rows, no d x d covariance, serial worker loop.
+        self.covariance = covariance
+        free = covariance == "free"
         # "projector" (default, the reference's server): top-k of the projector average;
         # "procrustes": Procrustes-aligned average of the bases, reference V_1.
         self.aggregator = aggregate
@@ -155,15 +183,15 @@ class DistributedEigenspaceEstimator:
         # concurrent_workers (default GPU worker, W > 1): covariances back to back on
         # the caller's stream, each worker's eigensolve in a my_threading.Slave
         # thread on its own HIP stream, chained by an event (bench.py's c5 mode).
-        self.concurrent = bool(concurrent_workers) and worker_fn is None
+        self.concurrent = bool(concurrent_workers) and worker_fn is None and not free
         # batched_workers (default GPU worker, W > 1, unless concurrent_workers): the W
         # covariances back to back, then ONE batched solve (linalg.topk_eigh_batch:
         # same results as W topk_eigh calls, the small Rayleigh-Ritz solves of all
         # workers in one launch per step).
-        self.batched = bool(batched_workers) and worker_fn is None and not self.concurrent
+        self.batched = bool(batched_workers) and worker_fn is None and not self.concurrent and not free
         self.server_rank = server_rank
         self.group = group
-        self.worker_fn = worker_fn or _gpu_worker
+        self.worker_fn = worker_fn or (_gpu_worker_free if free else _gpu_worker)
         self.solver_kw = dict(solver_kw or {})
         # center (opt-in): the eigenspace of the covariance about the pooled mean of all
         # ranks' rows; the default stays the reference's uncentred second moment.

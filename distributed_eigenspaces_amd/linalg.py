@@ -28,6 +28,7 @@ __all__ = [
     "column_sums", "sigma_hat_centered", "pca_transform",
     "column_sums_u8", "sigma_hat_u8_centered", "pca_transform_u8",
     "sigma_hat_bf16", "bf16_device_tensor",
+    "gram_apply", "topk_samples",
 ]
 
 DEFAULT_TOL = 1e-6
@@ -788,6 +789,104 @@ def projavg_topk(Wt: torch.Tensor, k: int, scale: float, *, p: int | None = None
                 ctypes.byref(resid), o),
                "deig_projavg_workspace_ex", (dp, mk, k, pp, o))
     res = _finish(rc, V, evals, sweeps, resid, "deig_projavg_topk_ex")
+    if dp != d:
+        res.V = res.V[:d].t().contiguous().t()
+    return res
+
+
+# ---------------------------------------------------------------- covariance-free route
+def _sample_operands(X, center, name: str):
+    """``(X, xtype, n, d, dp, center)`` of a covariance-free call: float32, bfloat16 and 2-D
+    uint8 samples are read where they lie when strides and alignment allow (the rules of
+    ``_oja_in_place``, and d >= 16), otherwise from a zero-padded copy of the SAME dtype with
+    dp columns; ``center`` as float64 on the device, zero-padded alike (a padded column stages
+    fl32(0 - 0) = 0).  float64 samples raise: the route's products are float32."""
+    if isinstance(X, torch.Tensor) and X.dtype == torch.float64:
+        raise TypeError(f"{name}: float64 samples are not supported by the covariance-free route; "
+                        "use the explicit route (sigma_hat / sigma_hat_centered + topk_eigh), which "
+                        "reads float64 in double")
+    if isinstance(X, torch.Tensor) and X.dtype in (torch.uint8, torch.bfloat16):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
+        if X.device.type != "cuda":
+            X = X.to(torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if not isinstance(X, torch.Tensor) and getattr(X, "dtype", None) == "float64":
+            raise TypeError(f"{name}: float64 samples are not supported by the covariance-free "
+                            "route; use the explicit route (sigma_hat + topk_eigh)")
+        X = require_device_tensor(X, name)
+    if X.dim() != 2 or X.shape[0] < 1:
+        raise ValueError(f"{name}: X must be 2-D with at least one row, got shape {tuple(X.shape)}")
+    n, d = X.shape
+    code, q, _ = _OJA_XTYPES[X.dtype]
+    dp = max(16, (d + q - 1) // q * q)
+    if dp != d or not _oja_in_place(X):
+        Xp = torch.zeros((n, dp), dtype=X.dtype, device=X.device)
+        Xp[:, :d] = X
+        X = Xp
+    c = None
+    if center is not None:
+        c = torch.as_tensor(center).to(device=X.device, dtype=torch.float64).reshape(-1)
+        if c.numel() != d:
+            raise ValueError(f"center must have d = {d} entries, got {c.numel()}")
+        if dp != d:
+            c = torch.cat([c, c.new_zeros(dp - d)])
+        elif c.stride(0) != 1 or c.data_ptr() % 8:
+            c = c.clone()
+    return X, getattr(_lib, code), n, d, dp, c
+
+
+def gram_apply(X: torch.Tensor, Q: torch.Tensor, center=None, alpha: float | None = None) -> torch.Tensor:
+    """``alpha * Xc^T (Xc Q)`` for the n x d samples X (float32, bfloat16 or uint8 raw bytes)
+    about ``center`` (d values, taken in float64; None: no centring), without forming d x d:
+    the operator of ``topk_samples`` (include/deig.h deig_gram_apply).  Q: (d, p) with p a
+    multiple of 16 in 16..128; alpha defaults to 1/n.  Returns the (d, p) float32 product."""
+    X, xtype, n, d, dp, c = _sample_operands(X, center, "gram_apply")
+    Q = require_device_tensor(Q, "Q")
+    if Q.dim() != 2 or Q.shape[0] != d or Q.device != X.device:
+        raise ValueError(f"Q must be a (d, p) = ({d}, p) tensor on X's device, got {tuple(Q.shape)}")
+    p = Q.shape[1]
+    if dp != d:
+        Qp = torch.zeros((dp, p), dtype=torch.float32, device=X.device)
+        Qp[:d] = Q
+        Q = Qp
+    elif Q.stride(1) != 1 or Q.stride(0) % 4 or Q.stride(0) < p or Q.data_ptr() % 16:
+        Q = Q.clone(memory_format=torch.contiguous_format)
+    Y = torch.empty((dp, p), dtype=torch.float32, device=X.device)
+    _call(X.device, "deig_gram_apply",
+          (X.data_ptr(), xtype, n, dp, _ld(X, 0, dp), _ptr(c), _alpha(alpha, n), Q.data_ptr(), p,
+           _ld(Q, 0, p), Y.data_ptr(), p),
+          "deig_gram_apply_workspace", (n, dp, p, xtype))
+    return Y[:d] if dp != d else Y
+
+
+def topk_samples(X: torch.Tensor, k: int, center=None, alpha: float | None = None, *,
+                 p: int | None = None, tol: float = DEFAULT_TOL, max_sweeps: int = DEFAULT_MAX_SWEEPS,
+                 q0: torch.Tensor | None = None, opts: "_lib.SolverOpts | None" = None) -> EigResult:
+    """Top-k eigenpairs (ascending) of ``alpha * Xc^T Xc`` straight from the n x d samples,
+    never forming the d x d covariance: the covariance-free worker route (include/deig.h
+    deig_topk_samples).  X: float32, bfloat16 or uint8 (raw bytes) samples, read where they
+    lie; ``center``: d values subtracted in double where a sample is staged (None: none);
+    alpha defaults to 1/n; 1 <= k <= 128.  Two reads of X per solver sweep, workspace
+    O((n_chunk + d) p): the route for n << d and for d beyond the covariance kernels.  The
+    operator is implicit, so a dominant mean direction is not deflated: centre such data
+    (``center=``) or use ``sigma_hat*`` + ``topk_eigh``."""
+    X, xtype, n, d, dp, c = _sample_operands(X, center, "topk_samples")
+    k = _check_k(k, d)
+    q, k0, ldq = _warm(q0, d, X.device)
+    if q is not None and dp != d:
+        qp = torch.zeros((dp, k0), dtype=torch.float32, device=X.device)
+        qp[:d] = q
+        q, ldq = qp.t().contiguous().t(), dp
+    pp = int(p) if p else default_subspace(dp, k)
+    o = ctypes.byref(opts if opts is not None else _lib.solver_opts())
+    V, evals, sweeps, resid = _solver_outputs(dp, k, X.device)
+    rc = _call(X.device, "deig_topk_samples",
+               (X.data_ptr(), xtype, n, dp, _ld(X, 0, dp), _ptr(c), _alpha(alpha, n), k, pp,
+                int(max_sweeps), tol, _ptr(q), k0, ldq, V.data_ptr(), dp, evals.data_ptr(),
+                ctypes.byref(sweeps), ctypes.byref(resid), o),
+               "deig_topk_samples_workspace", (n, dp, k, pp, xtype, o))
+    res = _finish(rc, V, evals, sweeps, resid, "deig_topk_samples")
     if dp != d:
         res.V = res.V[:d].t().contiguous().t()
     return res

@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 
 from . import linalg
-from .estimator import DistributedEigenspaceEstimator, comm_tensor
+from .estimator import COVARIANCES, DistributedEigenspaceEstimator, comm_tensor
 from .streaming import broadcast_basis
 
 __all__ = ["PCA"]
@@ -53,10 +53,19 @@ class PCA:
     """
 
     def __init__(self, k: int, *, workers_per_rank: int = 1, group=None,
-                 aggregate: str = "projector", solver_kw=None, u8_mode: str | None = None):
+                 aggregate: str = "projector", solver_kw=None, u8_mode: str | None = None,
+                 covariance: str = "explicit"):
         if u8_mode is not None and u8_mode not in ("raw", "gray"):
             raise ValueError(f"u8_mode must be None, 'raw' or 'gray', got {u8_mode!r}")
+        if covariance not in COVARIANCES:
+            raise ValueError(f"covariance must be one of {COVARIANCES}, got {covariance!r}")
+        if covariance == "free" and u8_mode == "gray":
+            raise ValueError("covariance='free' reads uint8 samples as raw bytes only: "
+                             "u8_mode='gray' needs covariance='explicit'")
         self.u8_mode = u8_mode
+        # the estimator's worker route: "explicit" covariances (default) or "free"
+        # (linalg.topk_samples on the rows; float32, bfloat16 and raw uint8 samples)
+        self.covariance = covariance
         self.k = int(k)
         self.wpr = int(workers_per_rank)
         self.group = group
@@ -107,7 +116,8 @@ class PCA:
         est = DistributedEigenspaceEstimator(k, workers_per_rank=self.wpr, group=self.group,
                                              server_rank=self.server_rank,
                                              aggregate=self.aggregate, solver_kw=self.solver_kw,
-                                             center=True, u8_mode=self.u8_mode)
+                                             center=True, u8_mode=self.u8_mode,
+                                             covariance=self.covariance)
         r = est.fit(X)
         d = r.mean.numel()  # the features (of a gray fit: the pixels)
         Vt = torch.empty((k, d), dtype=torch.float32, device=X.device)

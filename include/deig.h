@@ -47,8 +47,9 @@ extern "C" {
  * bits of the fp32 value, as torch.bfloat16 and __bf16 store it; alignment 2 bytes.  Widening
  * is exact, so these entry points return the bits they return for the fp32 copy. */
 #define DEIG_BF16 2
-/* Raw bytes (uint8), one feature per byte: element type of deig_oja_steps_centered only (the
- * one-shot uint8 entry points take their own DEIG_U8_* modes); alignment 4 bytes. */
+/* Raw bytes (uint8), one feature per byte: element type of deig_oja_steps_centered,
+ * deig_gram_apply and deig_topk_samples only (the covariance and transform uint8 entry points
+ * take their own DEIG_U8_* modes); alignment 4 bytes. */
 #define DEIG_U8 3
 
 /* Library version, e.g. 0x000400 for 0.4.0.  A caller built against an older header
@@ -586,6 +587,53 @@ int deig_oja_steps_bf16(const void* X, int64_t nb, int64_t b, int64_t d, int64_t
 int deig_oja_steps_centered(const void* X, int xtype, int64_t nb, int64_t b, int64_t d,
                             int64_t ldx, const double* center, float eta, float* V, int k,
                             int64_t ldv, int orth_every, void* ws, size_t ws_bytes, void* stream);
+
+/* Covariance-free worker solve: the top-k eigenpairs of  scale * Xc^T Xc  straight from the
+ * samples, without forming a d x d matrix (n << d: wide data with few rows, and d beyond the
+ * covariance routes' reach).  Xc[r][j] = fl32((double)x_rj - center[j]), formed in double and
+ * rounded once where a value is staged (center == NULL: the exact widening of x).
+ *
+ * deig_gram_apply is the operator itself,  Y = alpha * Xc^T (Xc Q),  exposed for testing and
+ * reuse as deig_sym_apply_f32 is for the sweeps.  Two products per call, X read twice, in
+ * chunks of rows: Zt = Xc Q (chunk x p, in the workspace) by the fused transform kernels of
+ * deig_pca_transform_*, then Y (+)= alpha Xc^T Zt by a packed-sample TN kernel with split-K
+ * partial slabs summed in slice order; the chunks are added in chunk order.
+ * X: n x d row-major of element type xtype, row stride ldx elements (DEIG_U8: raw bytes),
+ * n >= 1, d >= 16, ldx >= d:
+ *   DEIG_F32:  16-byte aligned, d % 4 == 0, ldx % 4 == 0;
+ *   DEIG_BF16: 16-byte aligned, d % 8 == 0, ldx % 8 == 0;
+ *   DEIG_U8:   4-byte aligned,  d % 4 == 0, ldx % 4 == 0;
+ * DEIG_F64 or any other xtype is DEIG_EINVAL.  No element behind column d of a row is read.
+ * center: d doubles on the device, in units of x, or NULL.  Q, Y: d x p row-major, 16-byte
+ * aligned, ldq % 4 == 0, ldy % 4 == 0, both >= p; p % 16 == 0, 16 <= p <= 128.  Nothing behind
+ * column p of a Y row is written.
+ * Workspace: deig_gram_apply_workspace(n, d, p, xtype) is the recommended size (0 for shapes
+ * the call rejects; it does not decrease in n or p).  Any workspace of at least
+ * deig_gram_apply_workspace(n', d, p, xtype) bytes for some 1 <= n' <= n is accepted and sets
+ * the chunk (deig_syrk_bf16's rule).  It may hold anything on entry.
+ * Asynchronous on `stream`: no allocation, no synchronisation, no atomics; repeated calls give
+ * identical bits.  Argument errors are DEIG_EINVAL with a message naming the rule, a short or
+ * NULL workspace is DEIG_EWORKSPACE, both before any GPU work.
+ *
+ * deig_topk_samples runs the solver of deig_projavg_topk_ex on that operator (implicit: no
+ * image, exact Rayleigh-Ritz, its jcap defaults): the same outputs, return codes and stopping
+ * rule; V d x k column-major (ldv >= d), evals ascending: the eigenvalues of scale * Xc^T Xc.
+ * 1 <= k <= min(128, d); p % 16 == 0, 16 <= p <= 128, k <= p <= d.  Single solves only.
+ * Implicit operators have no dominant-pair deflation: uncentred data with a large mean keeps
+ * the fp32 cancellation of the small directions against the mean direction that the explicit
+ * route (deig_topk_sym_ex on a covariance) deflates away - pass `center`, or use that route.
+ * Additive: probe for the symbols, deig_version() is unchanged. */
+int deig_gram_apply(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                    const double* center, float alpha, const float* Q, int p, int64_t ldq,
+                    float* Y, int64_t ldy, void* ws, size_t ws_bytes, void* stream);
+size_t deig_gram_apply_workspace(int64_t n, int64_t d, int p, int xtype);
+int deig_topk_samples(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                      const double* center, float scale, int k, int p, int max_sweeps, float tol,
+                      const float* Q0, int k0, int64_t ldq0, float* V, int64_t ldv, float* evals,
+                      int* sweeps_out, float* resid_out, const deig_solver_opts* opts,
+                      void* ws, size_t ws_bytes, void* stream);
+size_t deig_topk_samples_workspace(int64_t n, int64_t d, int k, int p, int xtype,
+                                   const deig_solver_opts* opts);
 
 /* Projection onto an estimated eigenspace: Y = X W.
  * Replaces the notebook's  online_distributed_PCA = lambda X: X @ matrix_w
