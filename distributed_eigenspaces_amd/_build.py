@@ -25,7 +25,7 @@ SOURCES = ["capi.hip", "solver.hip", "syrk.hip", "syrk_split.hip", "syrk_u8.hip"
 # (profiles/pca_transform_packed_refactor.json).
 EXTRA_FLAGS = {"sweep.hip": ["-fno-slp-vectorize"], "syrk_split.hip": ["-fno-slp-vectorize"],
                "pca_bf16.hip": ["-Xarch_device", "-falign-loops=64"]}
-HEADERS = ["deig_internal.hpp", "skinny_tile.hpp", "pca_packed_tile.hpp", "syrk_image_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
+HEADERS = ["deig_internal.hpp", "sample_src.hpp", "skinny_tile.hpp", "pca_packed_tile.hpp", "syrk_image_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
 # Test-only variant (tests/test_gpu_oja_timeout.py): oja.hip with a zero spin bound, so
 # every resident hand-off times out and the DEIG_ETIMEOUT report can be exercised; the
 # other objects are the shipped library's.

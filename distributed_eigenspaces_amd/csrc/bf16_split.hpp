@@ -1,9 +1,9 @@
 // fp32 -> bf16 pieces for the split products (x = hi + lo (+ ...), each piece a bf16):
-// the packed conversion and its two halves read back as fp32, and the vector types of
-// the bf16 MFMA operands (syrk_split.hip, sweep.hip, oja.hip).
+// the packed conversion (its two halves read back as fp32: lo_f / hi_f, sample_src.hpp) and
+// the vector types of the bf16 MFMA operands (syrk_split.hip, sweep.hip, oja.hip).
 #pragma once
 
-#include "deig_internal.hpp"
+#include "sample_src.hpp"
 
 namespace deig {
 
@@ -17,7 +17,5 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint32_t cvt2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
-__device__ __forceinline__ float lo_f(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
 
 }  // namespace deig

@@ -42,10 +42,6 @@ struct bf16_t {
   __host__ __device__ explicit operator double() const { return (double)(float)*this; }
 };
 
-// Bytes of an element of type xtype (DEIG_F32 / DEIG_F64 / DEIG_BF16): its alignment rule.
-inline size_t elem_bytes(int xtype) { return xtype == DEIG_F64 ? 8 : xtype == DEIG_BF16 ? 2 : 4; }
-inline bool known_elem(int xtype) { return xtype == DEIG_F32 || xtype == DEIG_F64 || xtype == DEIG_BF16; }
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

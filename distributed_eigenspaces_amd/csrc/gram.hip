@@ -15,9 +15,9 @@
 //     80) and float4 LDS stores of skinny_kernel's transposed path.
 //     Staging map, the same for the three sources: element group f = tid + 256 u (u = 0, 1)
 //     is row f >> 4 of the chunk and features 4 (f & 15) .. + 3 of the tile: a 16-byte load of
-//     float32, 8 bytes of bf16, one dword of bytes.  A thread's features are the same in every
-//     chunk, so its four centre entries are loaded once before the K loop.  Centring is a
-//     uniform run-time branch where a value is staged (one rounding, as ptile::Src::value);
+//     float32, 8 bytes of bf16, one dword of bytes (SampleGroup, sample_src.hpp).  A thread's
+//     features are the same in every chunk, so its four centre entries are loaded once before
+//     the K loop.  Centring is a uniform run-time branch where a value is staged (centre1);
 //     rows past the chunk and features past d stage exact zeros; d is a multiple of the load
 //     group, so nothing behind column d of a row is read.
 //     A chunk row of a tile is 256 B of float32, 128 B of bf16 and 64 B of bytes - half a cache
@@ -27,6 +27,7 @@
 //     Split-K over the chunk's rows: fp32 partial slabs summed in slice order by
 //     skinny_reduce_kernel, which also applies alpha and adds the chunks before (beta = 1 from
 //     the second chunk on).  Fixed order, no atomics: repeated calls give identical bits.
+#include "sample_src.hpp"
 #include "skinny_tile.hpp"
 
 namespace deig {
@@ -34,36 +35,6 @@ namespace {
 
 constexpr int GBM = tile::kRows, GBK = tile::kChunk;
 constexpr int GT = tile::kThreads, GAST = tile::kAStridePadded;
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// A sample source: Elem, the raw group of four features (Raw), its load and feature e of it.
-struct GramF32 {
-  using Elem = float;
-  using Raw = f32x4;
-  static __device__ __forceinline__ Raw zero() { return Raw{0.f, 0.f, 0.f, 0.f}; }
-  static __device__ __forceinline__ Raw load(const Elem* p) { return *reinterpret_cast<const Raw*>(p); }
-  static __device__ __forceinline__ float value(const Raw& x, int e) { return x[e]; }
-};
-struct GramBf16 {
-  using Elem = uint16_t;
-  using Raw = u32x2;
-  static __device__ __forceinline__ Raw zero() { return Raw{0u, 0u}; }
-  static __device__ __forceinline__ Raw load(const Elem* p) { return *reinterpret_cast<const Raw*>(p); }
-  static __device__ __forceinline__ float value(const Raw& x, int e) {
-    const uint32_t w = x[e >> 1];
-    return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));  // exact widening
-  }
-};
-struct GramU8 {
-  using Elem = uint8_t;
-  using Raw = uint32_t;
-  static __device__ __forceinline__ Raw zero() { return 0u; }
-  static __device__ __forceinline__ Raw load(const Elem* p) { return *reinterpret_cast<const Raw*>(p); }
-  static __device__ __forceinline__ float value(const Raw& x, int e) {
-    return (float)((x >> (8 * e)) & 0xffu);
-  }
-};
 
 // C[d x N] (ldc) = alpha Xc^T B + beta C for the K rows of X at X (ks == 1), or slice sl's
 // partial sums into part[sl][d][N].  B: K x N row-major, row stride N.
@@ -142,7 +113,7 @@ __global__ __launch_bounds__(GT) void gram_tn_kernel(const typename Src::Elem* _
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float v = Src::value(ra[u], e);
-        t[e] = centred ? (live[u] ? (float)((double)v - mu[e]) : 0.f) : v;
+        t[e] = centred ? (live[u] ? centre1(v, mu[e]) : 0.f) : v;
       }
       *reinterpret_cast<f32x4*>(as + (arow + 16 * u) * GAST + 4 * c4) = t;
     }
@@ -191,16 +162,35 @@ __global__ __launch_bounds__(GT) void gram_tn_kernel(const typename Src::Elem* _
   }
 }
 
-size_t elem_size(int xtype) { return xtype == DEIG_F32 ? 4 : xtype == DEIG_BF16 ? 2 : 1; }
-
 // Split-K of the second product over a chunk of K rows: skinny.hip's rule (about four blocks
 // per CU, at least 8 inner chunks per slice).  Does not decrease in K.
 int gram_ks(int64_t d, int64_t K) { return skinny_split_k(d, K); }
 
-size_t transform_ws(int xtype, int64_t rows, int64_t d, int p) {
-  return xtype == DEIG_F32    ? pca_transform_workspace_bytes(rows, d, p)
-         : xtype == DEIG_BF16 ? pca_transform_bf16_workspace_bytes(rows, d, p)
-                              : pca_transform_u8_workspace_bytes(rows, d, p);
+// The first product Zt = Xc Q (rows x p, Y only) and its workspace, per sample type: the three
+// fused transform launchers behind one signature.
+size_t transform_ws(SampleGroup<float>, int64_t rows, int64_t d, int p) {
+  return pca_transform_workspace_bytes(rows, d, p);
+}
+size_t transform_ws(SampleGroup<bf16_t>, int64_t rows, int64_t d, int p) {
+  return pca_transform_bf16_workspace_bytes(rows, d, p);
+}
+size_t transform_ws(SampleGroup<uint8_t>, int64_t rows, int64_t d, int p) {
+  return pca_transform_u8_workspace_bytes(rows, d, p);
+}
+int transform(SampleGroup<float>, const void* X, int64_t rows, int64_t d, int64_t ldx, const double* center,
+              const float* Q, int p, int64_t ldq, float* Zt, void* ws, size_t ws_bytes, hipStream_t st) {
+  return pca_transform_launch(static_cast<const float*>(X), rows, d, ldx, center, Q, p, ldq, Zt, p, nullptr,
+                              nullptr, ws, ws_bytes, st, true);
+}
+int transform(SampleGroup<bf16_t>, const void* X, int64_t rows, int64_t d, int64_t ldx, const double* center,
+              const float* Q, int p, int64_t ldq, float* Zt, void* ws, size_t ws_bytes, hipStream_t st) {
+  return pca_transform_bf16_launch(X, rows, d, ldx, center, Q, p, ldq, Zt, p, nullptr, nullptr, ws, ws_bytes,
+                                   st, true);
+}
+int transform(SampleGroup<uint8_t>, const void* X, int64_t rows, int64_t d, int64_t ldx, const double* center,
+              const float* Q, int p, int64_t ldq, float* Zt, void* ws, size_t ws_bytes, hipStream_t st) {
+  return pca_transform_u8_launch(static_cast<const uint8_t*>(X), rows, d, ldx, DEIG_U8_RAW, center, Q, p, ldq,
+                                 Zt, p, nullptr, nullptr, ws, ws_bytes, st, true);
 }
 
 struct GramWs {
@@ -215,7 +205,7 @@ GramWs carve_gram(void* ws, size_t cap, int64_t rows, int64_t d, int p, int xtyp
   Carve c(ws, cap);
   GramWs g;
   g.Zt = c.take<float>((size_t)rows * p);
-  g.tw_bytes = transform_ws(xtype, rows, d, p);
+  g.tw_bytes = dispatch_sample(xtype, [&](auto s) { return transform_ws(s, rows, d, p); });
   g.tw = c.take<char>(g.tw_bytes);
   const int ks = gram_ks(d, rows);
   g.slab = c.take<float>(ks > 1 ? (size_t)ks * d * p : 0);
@@ -224,8 +214,8 @@ GramWs carve_gram(void* ws, size_t cap, int64_t rows, int64_t d, int p, int xtyp
 }
 
 bool gram_shape_ok(int64_t n, int64_t d, int p, int xtype) {
-  if (xtype != DEIG_F32 && xtype != DEIG_BF16 && xtype != DEIG_U8) return false;
-  const int q = xtype == DEIG_BF16 ? 8 : 4;
+  if (!sample_type(xtype)) return false;
+  const int q = kSampleRules[xtype].group;
   return n >= 1 && d >= 16 && d % q == 0 && d <= (int64_t(1) << 31) - 64 && p >= 16 && p <= 128 &&
          p % 16 == 0;
 }
@@ -274,10 +264,9 @@ size_t gram_apply_workspace_bytes(int64_t n, int64_t d, int p, int xtype) {
 
 int gram_apply_check(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
                      const char* what) {
-  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_BF16 || xtype == DEIG_U8,
-               "%s: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got %d)", what, xtype);
-  const int q = xtype == DEIG_BF16 ? 8 : 4;
-  const size_t xalign = xtype == DEIG_U8 ? 4 : 16;
+  DEIG_REQUIRE(sample_type(xtype), "%s: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got %d)", what, xtype);
+  const int q = kSampleRules[xtype].group;
+  const size_t xalign = kSampleRules[xtype].align;
   DEIG_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
   DEIG_REQUIRE(d >= 16, "%s: d must be >= 16 (got %lld)", what, (long long)d);
   DEIG_REQUIRE(d % q == 0 && d <= (int64_t(1) << 31) - 64, "%s: d must be a multiple of %d (got %lld)",
@@ -319,30 +308,15 @@ int gram_apply_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
       hi = mid - 1;
   }
   const int64_t chunk = lo;
-  const size_t es = elem_size(xtype);
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
     const GramWs g = carve_gram(ws, ws_bytes, rows, d, p, xtype, &total);
-    const char* Xr = static_cast<const char*>(X) + (size_t)r0 * ldx * es;
-    int rc;
-    if (xtype == DEIG_F32)
-      rc = pca_transform_launch(reinterpret_cast<const float*>(Xr), rows, d, ldx, center, Q, p, ldq, g.Zt,
-                                p, nullptr, nullptr, g.tw, g.tw_bytes, st, true);
-    else if (xtype == DEIG_BF16)
-      rc = pca_transform_bf16_launch(Xr, rows, d, ldx, center, Q, p, ldq, g.Zt, p, nullptr, nullptr, g.tw,
-                                     g.tw_bytes, st, true);
-    else
-      rc = pca_transform_u8_launch(reinterpret_cast<const uint8_t*>(Xr), rows, d, ldx, DEIG_U8_RAW, center,
-                                   Q, p, ldq, g.Zt, p, nullptr, nullptr, g.tw, g.tw_bytes, st, true);
-    if (rc) return rc;
-    const int ks = gram_ks(d, rows);
-    const float beta = r0 ? 1.f : 0.f;
-    if (xtype == DEIG_F32)
-      rc = launch_tn<GramF32>(Xr, ldx, center, g.Zt, Y, ldy, d, rows, p, alpha, beta, g.slab, ks, st);
-    else if (xtype == DEIG_BF16)
-      rc = launch_tn<GramBf16>(Xr, ldx, center, g.Zt, Y, ldy, d, rows, p, alpha, beta, g.slab, ks, st);
-    else
-      rc = launch_tn<GramU8>(Xr, ldx, center, g.Zt, Y, ldy, d, rows, p, alpha, beta, g.slab, ks, st);
+    const char* Xr = static_cast<const char*>(X) + (size_t)r0 * ldx * elem_bytes(xtype);
+    const int rc = dispatch_sample(xtype, [&](auto s) {
+      if (int e = transform(s, Xr, rows, d, ldx, center, Q, p, ldq, g.Zt, g.tw, g.tw_bytes, st)) return e;
+      return launch_tn<decltype(s)>(Xr, ldx, center, g.Zt, Y, ldy, d, rows, p, alpha, r0 ? 1.f : 0.f, g.slab,
+                                    gram_ks(d, rows), st);
+    });
     if (rc) return rc;
   }
   return DEIG_OK;

@@ -12,9 +12,9 @@
 // type: a bf16 value is its own hi piece, so two MFMAs per fragment pair instead of three
 // and half the bytes of Xb, with the bits of the float kernels on the widened samples.
 // deig_oja_steps_centered adds raw bytes as a third sample type (exact in bf16: two MFMAs,
-// a quarter of the bytes) and a centred variant of every loader: the staged value is
-// fl32((double)x - mean[j]), one rounding, split into hi / lo (three MFMAs whatever the
-// sample type), with the bits of the float kernels on the matrix of those staged values.
+// a quarter of the bytes) and a centred variant of every loader: the staged sample
+// (sample_src.hpp) is split into hi / lo (three MFMAs whatever the sample type), with the
+// bits of the float kernels on the matrix of those staged values.
 #include <algorithm>
 #include <type_traits>
 
@@ -249,66 +249,48 @@ __global__ __launch_bounds__(256) void trsm_img_kernel(const float* __restrict__
   }
 }
 
-// The sample type of the two passes: float samples are split into hi / lo bf16 pieces in
-// registers (three MFMAs per fragment pair); a bf16 sample (OjaBf16: the upper 16 bits of
-// the float, as torch.bfloat16 stores it) IS its hi piece and its lo piece is exactly zero,
-// so the third MFMA (lo hi) of the float kernels would add an exact zero and is left out:
-// the same k-steps in the same order, hence the bits of the float kernels on the widened
-// samples, from half the bytes.
-typedef __bf16 OjaBf16;
-// Raw bytes (DEIG_U8): a byte is exact in bf16, so, like a bf16 sample, it is its own hi piece
-// with a zero lo piece.  d % 4 == 0 and 4-byte alignment are all a row promises: 4-byte loads.
-typedef uint8_t OjaU8;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float oja_byte(uint32_t w, int e) { return (float)((w >> (8 * e)) & 0xffu); }
-// Centring at staging (ptile::Src::value): formed in double, rounded once.
-__device__ __forceinline__ float oja_centre(float x, double mu) { return (float)((double)x - mu); }
-
+// The sample type XT of the two passes (the element types of sample_src.hpp): float samples
+// are split into hi / lo bf16 pieces in registers (three MFMAs per fragment pair); a bf16
+// sample IS its hi piece and its lo piece is exactly zero, so the third MFMA (lo hi) of the
+// float kernels would add an exact zero and is left out: the same k-steps in the same order,
+// hence the bits of the float kernels on the widened samples, from half the bytes.  A raw byte
+// is exact in bf16, so, like a bf16 sample, it is its own hi piece with a zero lo piece.
+//
 // NN operand: a lane's 8 consecutive features of one row (p: the row, k: first feature,
 // clamped so that nothing behind column d is read) and its A fragments.  kGroup: the
 // features that one clamp covers (feature e of the lane is column
 // min(k + kGroup (e / kGroup), d - kGroup) + e % kGroup: the mean's index, oja_mean8);
-// get(e): feature e as a float, for the centred kernels.
+// get(e): feature e as a float, for the centred kernels.  Floats and bytes: two 4-feature
+// groups (d % 4 == 0 and the group's alignment are all a row promises).
 template <typename XT>
-struct OjaRow8;
-template <>
-struct OjaRow8<float> {
-  static constexpr bool kLo = true;
+struct OjaRow8 {
+  using G = SampleGroup<XT>;
+  static constexpr bool kLo = std::is_same<XT, float>::value;
   static constexpr int kGroup = 4;
-  f32x4 a, b;
-  __device__ __forceinline__ void load(const float* p, int k, int d) {
-    a = *reinterpret_cast<const f32x4*>(p + min(k, d - 4));
-    b = *reinterpret_cast<const f32x4*>(p + min(k + 4, d - 4));
+  typename G::Raw a, b;
+  __device__ __forceinline__ void load(const XT* p, int k, int d) {
+    a = G::load(p + min(k, d - 4));
+    b = G::load(p + min(k + 4, d - 4));
   }
-  __device__ __forceinline__ void frags(bf16x8& hi, bf16x8& lo) const { split8(a, b, hi, lo); }
-  __device__ __forceinline__ float get(int e) const { return e < 4 ? a[e] : b[e - 4]; }
+  __device__ __forceinline__ float get(int e) const { return e < 4 ? G::value(a, e) : G::value(b, e - 4); }
+  __device__ __forceinline__ void frags(bf16x8& hi, bf16x8& lo) const {
+    if constexpr (kLo)
+      split8(a, b, hi, lo);
+    else
+      hi = __builtin_bit_cast(bf16x8, u32x4{cvt2(get(0), get(1)), cvt2(get(2), get(3)), cvt2(get(4), get(5)),
+                                            cvt2(get(6), get(7))});
+  }
 };
 template <>
-struct OjaRow8<OjaBf16> {  // one 16-byte load, already the fragment (d % 8 == 0)
+struct OjaRow8<bf16_t> {  // one 16-byte load, already the fragment (d % 8 == 0)
   static constexpr bool kLo = false;
   static constexpr int kGroup = 8;
   u32x4 a;
-  __device__ __forceinline__ void load(const OjaBf16* p, int k, int d) {
+  __device__ __forceinline__ void load(const bf16_t* p, int k, int d) {
     a = *reinterpret_cast<const u32x4*>(p + min(k, d - 8));
   }
   __device__ __forceinline__ void frags(bf16x8& hi, bf16x8&) const { hi = __builtin_bit_cast(bf16x8, a); }
-  __device__ __forceinline__ float get(int e) const { return (e & 1) ? hi_f(a[e >> 1]) : lo_f(a[e >> 1]); }
-};
-template <>
-struct OjaRow8<OjaU8> {  // two 4-byte loads at the float loader's clamps
-  static constexpr bool kLo = false;
-  static constexpr int kGroup = 4;
-  uint32_t a, b;
-  __device__ __forceinline__ void load(const OjaU8* p, int k, int d) {
-    a = *reinterpret_cast<const uint32_t*>(p + min(k, d - 4));
-    b = *reinterpret_cast<const uint32_t*>(p + min(k + 4, d - 4));
-  }
-  __device__ __forceinline__ float get(int e) const { return e < 4 ? oja_byte(a, e) : oja_byte(b, e - 4); }
-  __device__ __forceinline__ void frags(bf16x8& hi, bf16x8&) const {
-    hi = __builtin_bit_cast(bf16x8, u32x4{cvt2(get(0), get(1)), cvt2(get(2), get(3)), cvt2(get(4), get(5)),
-                                          cvt2(get(6), get(7))});
-  }
+  __device__ __forceinline__ float get(int e) const { return bf16_f(a[e >> 1], e); }
 };
 // The mean entries of a lane's 8 features at the loader's clamped columns (nothing behind
 // mean[d - 1] is read).
@@ -322,29 +304,6 @@ __device__ __forceinline__ void oja_mean8(const double* __restrict__ mean, int k
   }
 }
 
-// TN operand: a lane's 4 consecutive features of one row, read back as floats for the
-// [feature][row] transpose region (bf16: one 8-byte load, bytes: one 4-byte load, widened on
-// the way in).
-template <typename XT>
-struct OjaSeg4;
-template <>
-struct OjaSeg4<float> {
-  f32x4 v;
-  __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const f32x4*>(p); }
-  __device__ __forceinline__ float get(int e) const { return v[e]; }
-};
-template <>
-struct OjaSeg4<OjaBf16> {
-  u32x2 v;
-  __device__ __forceinline__ void load(const OjaBf16* p) { v = *reinterpret_cast<const u32x2*>(p); }
-  __device__ __forceinline__ float get(int e) const { return (e & 1) ? hi_f(v[e >> 1]) : lo_f(v[e >> 1]); }
-};
-template <>
-struct OjaSeg4<OjaU8> {
-  uint32_t v;
-  __device__ __forceinline__ void load(const OjaU8* p) { v = *reinterpret_cast<const uint32_t*>(p); }
-  __device__ __forceinline__ float get(int e) const { return oja_byte(v, e); }
-};
 // The A fragments of 8 transposed values: split where the staged value has a lo piece (float
 // samples, and every centred value); widened bf16 values and bytes pack back exactly (round to
 // nearest of a bf16 value is the value).
@@ -375,9 +334,9 @@ constexpr int kOjaPF = 4;  // prefetch depth of the NN / TN passes (k-steps)
 // lane l holds row r0 + (l & 15), features 32 ks + 8 (l >> 4) .. + 7 (two float4
 // loads; the 16 rows x 128 B of a wave-instruction pair are whole lines), split to
 // hi / lo in registers; B from the V image (img_kernel), L2-resident.  Loads run
-// PF k-steps ahead of the MFMAs (register ring).  XT = OjaBf16: the lane's 8 features
+// PF k-steps ahead of the MFMAs (register ring).  XT = bf16_t: the lane's 8 features
 // are one 16-byte load that is the fragment itself (OjaRow8), features clamped to d - 8;
-// XT = OjaU8: two 4-byte loads, converted to the hi piece.  CEN: the staged value is
+// XT = uint8_t: two 4-byte loads, converted to the hi piece.  CEN: the staged value is
 // fl32((double)x - mean[j]) (j the loader's clamped column; the lane's 8 mean entries ride
 // the same register ring), split into hi / lo whatever the sample type - three products.
 template <int NB, typename XT, bool CEN>
@@ -421,7 +380,7 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, i
     if constexpr (CEN) {
       float v[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = oja_centre(xs[u].get(e), mu[u][e]);
+      for (int e = 0; e < 8; ++e) v[e] = centre1(xs[u].get(e), mu[u][e]);
       split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, ahi, alo);
     } else {
       xs[u].frags(ahi, alo);
@@ -489,12 +448,12 @@ __global__ __launch_bounds__(512) void oja_nn_kernel(const XT* __restrict__ X, i
 // 32 rows x 16 features with float4 loads (whole 64-B row segments) and transposes
 // them through its own LDS region ([feature][row], TS floats a row); B is the T
 // image (img_kernel).  An 8-feature group of the V image never straddles two
-// blocks (16 | 32), so each block writes its own image entries.  XT = OjaBf16: the
+// blocks (16 | 32), so each block writes its own image entries.  XT = bf16_t: the
 // same block shape and lane mapping with 8-byte loads (a lane's 4 features; a row
 // segment of the block is 32 B), widened on the way into the same LDS region, so the
 // region, the reads and every sum are the float kernel's; the blocks of one 128-B line
 // (4 instead of 2) are consecutive logical blocks, which xcd_logical keeps on one XCD.
-// XT = OjaU8: 4-byte loads (a row segment of the block is 16 B, 8 blocks a line).  CEN: a
+// XT = uint8_t: 4-byte loads (a row segment of the block is 16 B, 8 blocks a line).  CEN: a
 // lane's 4 features are the same in every k-step, so their 4 mean entries are loaded once,
 // before the loop, at the lane's clamped column; the value is centred on its way into LDS.
 template <int NB, typename XT, bool CEN>
@@ -533,12 +492,13 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const XT* __restrict__ X, i
   // loads run PF k-steps (32 rows each) ahead of their use (register ring): one
   // k-step in flight per wave was latency-bound (16 KiB per CU)
   constexpr int PF = kOjaPF;
-  OjaSeg4<XT> xa[PF], xb[PF];
+  using G = SampleGroup<XT>;  // a lane's 4 features of a row, widened on the way into LDS
+  typename G::Raw xa[PF], xb[PF];
   u32x4 bh[PF][NB], bl[PF][NB];
   auto load = [&](int ks, int slot) {
     const int64_t r = 32 * (int64_t)ks + (lane >> 2);
-    xa[slot].load(xb_ + min(r, b - 1) * ldx);
-    xb[slot].load(xb_ + min(r + 16, b - 1) * ldx);
+    xa[slot] = G::load(xb_ + min(r, b - 1) * ldx);
+    xb[slot] = G::load(xb_ + min(r + 16, b - 1) * ldx);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bh[slot][nb] = timg[img_index(ks, nb, 0, lane, NB)];
@@ -549,8 +509,8 @@ __global__ __launch_bounds__(512) void oja_tn_kernel(const XT* __restrict__ X, i
   auto step = [&](int u) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      T[(fl + e) * TS + rr] = CEN ? oja_centre(xa[u].get(e), mu[e]) : xa[u].get(e);
-      T[(fl + e) * TS + rr + 16] = CEN ? oja_centre(xb[u].get(e), mu[e]) : xb[u].get(e);
+      T[(fl + e) * TS + rr] = CEN ? centre1(G::value(xa[u], e), mu[e]) : G::value(xa[u], e);
+      T[(fl + e) * TS + rr + 16] = CEN ? centre1(G::value(xb[u], e), mu[e]) : G::value(xb[u], e);
     }
     const f32x4 a0 = *reinterpret_cast<const f32x4*>(T + (lane & 15) * TS + 8 * (lane >> 4));
     const f32x4 a1 = *reinterpret_cast<const f32x4*>(T + (lane & 15) * TS + 8 * (lane >> 4) + 4);
@@ -1160,7 +1120,7 @@ bool launch_oja_passes(int NB, const XT* Xb, int64_t ldx, int64_t b, int64_t d, 
   }
 }
 
-// The body of every entry point (arguments checked by the caller).  XT = OjaBf16 / OjaU8 and
+// The body of every entry point (arguments checked by the caller).  XT = bf16_t / uint8_t and
 // every centred call (mean != nullptr: d doubles on the device) run the two-pass kernels
 // only: they never ask for the CU count or the occupancy, never launch the resident kernel,
 // and so never set the timeout word they clear.
@@ -1270,64 +1230,51 @@ int oja_steps_launch(const float* X, int64_t nb, int64_t b, int64_t d, int64_t l
   return oja_steps_run(X, nb, b, d, ldx, nullptr, eta, V, k, ldv, orth_every, ws, ws_bytes, st, algo);
 }
 
-// bf16 samples as they are (include/deig.h deig_oja_steps_bf16): the two-pass kernels'
-// OjaBf16 instantiations, everything else of the call shared with the float path.
+// The packed entry points (include/deig.h): samples of type xtype as they are, about a centre
+// or not (center == NULL), on the two-pass kernels' instantiations for the sample type,
+// everything else of the call shared with the float path.  One list of rules, those of the
+// uncentred entry points and of deig_syrk_u8 (raw) per type (kSampleRules), reported under the
+// entry point's name `what`.
+static int oja_steps_packed(const char* what, const void* X, int xtype, int64_t nb, int64_t b, int64_t d,
+                            int64_t ldx, const double* center, float eta, float* V, int k, int64_t ldv,
+                            int orth_every, void* ws, size_t ws_bytes, hipStream_t st) {
+  DEIG_REQUIRE(sample_type(xtype), "%s: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got %d)", what, xtype);
+  const int q = kSampleRules[xtype].group;
+  const size_t xalign = kSampleRules[xtype].align;
+  DEIG_REQUIRE(nb >= 1, "%s: nb must be >= 1 (got %lld)", what, (long long)nb);
+  DEIG_REQUIRE(b >= 1, "%s: b must be >= 1 (got %lld)", what, (long long)b);
+  DEIG_REQUIRE(d >= q && d % q == 0, "%s: d must be a multiple of %d, at least %d (got %lld)", what, q, q,
+               (long long)d);
+  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "%s: need 1 <= k <= min(64, d) (got k=%d, d=%lld)", what, k,
+               (long long)d);
+  DEIG_REQUIRE(ldx >= d, "%s: ldx must be >= d", what);
+  DEIG_REQUIRE(ldx % q == 0, "%s: ldx must be a multiple of %d elements", what, q);
+  DEIG_REQUIRE(ldv >= d, "%s: ldv must be >= d", what);
+  DEIG_REQUIRE(orth_every >= 1, "%s: orth_every must be >= 1 (got %d)", what, orth_every);
+  DEIG_REQUIRE(X && V, "%s: X and V must not be NULL", what);
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(X) % xalign == 0, "%s: X must be %zu-byte aligned", what, xalign);
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(V) % sizeof(float) == 0, "%s: V must be aligned to its element size",
+               what);
+  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % sizeof(double) == 0,
+               "%s: center must be aligned to its element size", what);
+  return dispatch_sample(xtype, [&](auto s) {
+    return oja_steps_run(static_cast<const typename decltype(s)::Elem*>(X), nb, b, d, ldx, center, eta, V, k,
+                         ldv, orth_every, ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
+  });
+}
+
 int oja_steps_bf16_launch(const void* X, int64_t nb, int64_t b, int64_t d, int64_t ldx, float eta,
                           float* V, int k, int64_t ldv, int orth_every, void* ws, size_t ws_bytes,
                           hipStream_t st) {
-  DEIG_REQUIRE(nb >= 1, "oja_bf16: nb must be >= 1 (got %lld)", (long long)nb);
-  DEIG_REQUIRE(b >= 1, "oja_bf16: b must be >= 1 (got %lld)", (long long)b);
-  DEIG_REQUIRE(d >= 8 && d % 8 == 0, "oja_bf16: d must be a multiple of 8, at least 8 (got %lld)",
-               (long long)d);
-  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "oja_bf16: need 1 <= k <= min(64, d) (got k=%d, d=%lld)",
-               k, (long long)d);
-  DEIG_REQUIRE(ldx >= d, "oja_bf16: ldx must be >= d");
-  DEIG_REQUIRE(ldx % 8 == 0, "oja_bf16: ldx must be a multiple of 8 elements");
-  DEIG_REQUIRE(ldv >= d, "oja_bf16: ldv must be >= d");
-  DEIG_REQUIRE(orth_every >= 1, "oja_bf16: orth_every must be >= 1 (got %d)", orth_every);
-  DEIG_REQUIRE(X && V, "oja_bf16: X and V must not be NULL");
-  DEIG_REQUIRE(aligned16(X), "oja_bf16: X must be 16-byte aligned");
-  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(V) % sizeof(float) == 0,
-               "oja_bf16: V must be aligned to its element size");
-  return oja_steps_run(static_cast<const OjaBf16*>(X), nb, b, d, ldx, nullptr, eta, V, k, ldv,
-                       orth_every, ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
+  return oja_steps_packed("oja_bf16", X, DEIG_BF16, nb, b, d, ldx, nullptr, eta, V, k, ldv, orth_every, ws,
+                          ws_bytes, st);
 }
 
-// Samples of type xtype about a centre (include/deig.h deig_oja_steps_centered): the two-pass
-// kernels' centred instantiations (center == NULL: the uncentred ones), per-type shape rules
-// those of the uncentred entry points and of deig_syrk_u8 (raw).
 int oja_steps_centered_launch(const void* X, int xtype, int64_t nb, int64_t b, int64_t d, int64_t ldx,
                               const double* center, float eta, float* V, int k, int64_t ldv,
                               int orth_every, void* ws, size_t ws_bytes, hipStream_t st) {
-  DEIG_REQUIRE(xtype == DEIG_F32 || xtype == DEIG_BF16 || xtype == DEIG_U8,
-               "oja_centered: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got %d)", xtype);
-  const int q = xtype == DEIG_BF16 ? 8 : 4;  // elements of the narrowest load group
-  const size_t xalign = xtype == DEIG_U8 ? 4 : 16;
-  DEIG_REQUIRE(nb >= 1, "oja_centered: nb must be >= 1 (got %lld)", (long long)nb);
-  DEIG_REQUIRE(b >= 1, "oja_centered: b must be >= 1 (got %lld)", (long long)b);
-  DEIG_REQUIRE(d >= q && d % q == 0, "oja_centered: d must be a multiple of %d, at least %d (got %lld)", q,
-               q, (long long)d);
-  DEIG_REQUIRE(k >= 1 && k <= 64 && k <= d, "oja_centered: need 1 <= k <= min(64, d) (got k=%d, d=%lld)",
-               k, (long long)d);
-  DEIG_REQUIRE(ldx >= d, "oja_centered: ldx must be >= d");
-  DEIG_REQUIRE(ldx % q == 0, "oja_centered: ldx must be a multiple of %d elements", q);
-  DEIG_REQUIRE(ldv >= d, "oja_centered: ldv must be >= d");
-  DEIG_REQUIRE(orth_every >= 1, "oja_centered: orth_every must be >= 1 (got %d)", orth_every);
-  DEIG_REQUIRE(X && V, "oja_centered: X and V must not be NULL");
-  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(X) % xalign == 0, "oja_centered: X must be %zu-byte aligned",
-               xalign);
-  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(V) % sizeof(float) == 0,
-               "oja_centered: V must be aligned to its element size");
-  DEIG_REQUIRE(reinterpret_cast<uintptr_t>(center) % sizeof(double) == 0,
-               "oja_centered: center must be aligned to its element size");
-  if (xtype == DEIG_F32)
-    return oja_steps_run(static_cast<const float*>(X), nb, b, d, ldx, center, eta, V, k, ldv, orth_every,
-                         ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
-  if (xtype == DEIG_BF16)
-    return oja_steps_run(static_cast<const OjaBf16*>(X), nb, b, d, ldx, center, eta, V, k, ldv,
-                         orth_every, ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
-  return oja_steps_run(static_cast<const OjaU8*>(X), nb, b, d, ldx, center, eta, V, k, ldv, orth_every,
-                       ws, ws_bytes, st, DEIG_OJA_TWO_PASS);
+  return oja_steps_packed("oja_centered", X, xtype, nb, b, d, ldx, center, eta, V, k, ldv, orth_every, ws,
+                          ws_bytes, st);
 }
 
 // The timeout word of the last oja_steps_launch on this workspace (set by a resident

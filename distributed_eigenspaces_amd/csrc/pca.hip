@@ -16,6 +16,7 @@
 //    hold (8 threads per row): energy.
 // No split-K: parallelism comes from n (one workgroup per 64 rows), so a small n with a
 // large d under-fills the chip.  No atomics: repeated calls give identical bits.
+#include "sample_src.hpp"
 #include "skinny_tile.hpp"
 
 namespace deig {
@@ -82,8 +83,8 @@ __global__ __launch_bounds__(PT) void pca_transform_kernel(
       rb[u] = v;
     }
   };
-  // centring happens here: t = fl32(x - mean) in double, one rounding; rows past n and
-  // columns past d stay exactly zero
+  // centring happens here (centre1, sample_src.hpp); rows past n and columns past d stay
+  // exactly zero
   auto store = [&](int buf) {
     float* as = As + buf * PBK * PAST;
 #pragma unroll
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(PT) void pca_transform_kernel(
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = ra[u][e];
-        if (mean) t = rowlive[u] ? (float)((double)t - mu[e]) : 0.f;
+        if (mean) t = rowlive[u] ? centre1(t, mu[e]) : 0.f;
         en[u] = fmaf(t, t, en[u]);
         as[(4 * kq + e) * PAST + mm + 32 * u] = t;
       }

@@ -8,12 +8,12 @@ namespace deig {
 namespace {
 
 struct Bf16Source {
-  using Elem = uint16_t;
+  using Elem = bf16_t;
   static constexpr int F = 8, DW = 4, kXAlign = 16;
   static constexpr bool kShortTail = false;
 
   // one 16-byte load where the 8 features lie inside d (d % 8 == 0: in or out together)
-  static __device__ __forceinline__ void load(const uint16_t* row, bool live, int64_t kc, int64_t d,
+  static __device__ __forceinline__ void load(const bf16_t* row, bool live, int64_t kc, int64_t d,
                                               uint32_t (&x)[DW]) {
     ptile::u32x4 v = {0u, 0u, 0u, 0u};
     if (live && kc < d) v = *reinterpret_cast<const ptile::u32x4*>(row + kc);
@@ -22,9 +22,8 @@ struct Bf16Source {
   }
   static __device__ __forceinline__ float value(const uint32_t (&x)[DW], int c, int e, bool centred,
                                                 double mu) {
-    const uint32_t w = x[2 * c + (e >> 1)];
-    const float v = __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));  // exact widening
-    return centred ? (float)((double)v - mu) : v;
+    const float v = bf16_f(x[2 * c + (e >> 1)], e);
+    return centred ? centre1(v, mu) : v;
   }
 };
 
@@ -46,7 +45,7 @@ int pca_transform_bf16_launch(const void* X, int64_t n, int64_t d, int64_t ldx, 
                  "pca_transform_bf16: ldx must be >= d and a multiple of 8 elements");
     return (int)DEIG_OK;
   };
-  return ptile::launch<Bf16Source>("pca_transform_bf16", static_cast<const uint16_t*>(X), n, d, ldx,
+  return ptile::launch<Bf16Source>("pca_transform_bf16", static_cast<const bf16_t*>(X), n, d, ldx,
                                    mean, W, k, ldw, Y, ldy, resid, energy, ws, ws_bytes, st, check,
                                    w_rowmajor);
 }

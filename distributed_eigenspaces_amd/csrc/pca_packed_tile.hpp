@@ -56,6 +56,7 @@
 //   value(x, c, e, centred, mu) feature 4 c + e of x as a float, minus mu in double if centred
 #pragma once
 
+#include "sample_src.hpp"
 #include "skinny_tile.hpp"
 
 namespace deig {

@@ -47,7 +47,9 @@ struct U8Source {
 struct U8Raw : U8Source<1> {
   static __device__ __forceinline__ float value(const uint32_t (&x)[DW], int c, int e, bool centred,
                                                 double mu) {
-    const float v = (float)((x[c] >> (8 * e)) & 0xffu);  // one byte-to-float convert
+    // byte_f and centre1 (sample_src.hpp) as text, not as calls: through either helper the
+    // sixteen NB instantiations schedule their converts in another order (same instructions)
+    const float v = (float)((x[c] >> (8 * e)) & 0xffu);
     return centred ? (float)((double)v - mu) : v;
   }
 };
@@ -68,7 +70,7 @@ struct U8Gray3 : U8Source<3> {
     const double sd = (double)s, third = 1.0 / 3.0;
     const double q = sd * third;
     const double v = fma(fma(-3.0, q, sd), third, q);
-    return centred ? (float)(v - mu) : (float)v;
+    return centred ? centre1(v, mu) : (float)v;
   }
 };
 

@@ -25,7 +25,7 @@
 // c = 0 is deig_syrk_shift (delta = mu: the same launches on the same values, the same bits);
 // c = NULL is the shard's own mean (delta = 0).  The column sums of the first pass are also
 // an entry point of their own (deig_colsum).
-#include "deig_internal.hpp"
+#include "sample_src.hpp"
 
 namespace deig {
 

@@ -109,48 +109,74 @@ def require_device_tensor(t, name: str = "input", keep_f64: bool = False) -> tor
     return t
 
 
-def bf16_device_tensor(t: torch.Tensor, name: str = "input") -> torch.Tensor:
-    """A bfloat16 tensor on a ROCm device, kept bfloat16 (host tensors are copied over)."""
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
-    if t.dtype != torch.bfloat16:
-        raise ValueError(f"{name} needs bfloat16 samples, got {t.dtype}")
+def _to_device(t: torch.Tensor, name: str) -> torch.Tensor:
+    """``t`` on a ROCm device with its dtype kept (a host tensor is copied over)."""
     if t.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
         t = t.to(torch.device("cuda", torch.cuda.current_device()))
     return t
 
 
-def _rowmajor_8_bf16(t: torch.Tensor, name: str) -> torch.Tensor:
-    """``_rowmajor_4`` for bfloat16 samples: a 2-D row-major view with unit column stride,
-    columns and row stride % 8 == 0, 16-B aligned; anything else is copied into a zero-padded
-    BFLOAT16 tensor (never a float32 one), so what lies behind the columns never enters."""
-    if t.dim() != 2:
-        raise ValueError(f"{name} must be 2-D, got shape {tuple(t.shape)}")
-    ok = (t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1]
-          and t.shape[1] % 8 == 0 and t.data_ptr() % 16 == 0)
-    if ok:
-        return t
-    out = torch.zeros((t.shape[0], (t.shape[1] + 7) // 8 * 8), dtype=torch.bfloat16, device=t.device)
-    out[:, :t.shape[1]] = t
-    return out
+def bf16_device_tensor(t: torch.Tensor, name: str = "input") -> torch.Tensor:
+    """A bfloat16 tensor on a ROCm device, kept bfloat16 (host tensors are copied over)."""
+    if t.dtype != torch.bfloat16:
+        raise ValueError(f"{name} needs bfloat16 samples, got {t.dtype}")
+    return _to_device(t, name)
 
 
-def _rowmajor_4(t: torch.Tensor, name: str) -> torch.Tensor:
-    """2-D row-major view with unit column stride, columns and row stride % 4 == 0, 16-B
-    aligned; anything else (a 37-column slice of a 40-column tensor included) is copied
-    into a zero-padded tensor, so what lies behind the columns never enters."""
+def _rowmajor(t: torch.Tensor, name: str, q: int = 4) -> torch.Tensor:
+    """2-D row-major view with unit column stride, columns and row stride % q == 0 (4; 8 for
+    bfloat16 samples), 16-B aligned; anything else (a 37-column slice of a 40-column tensor
+    included) is copied into a zero-padded tensor of ``t``'s own dtype, so what lies behind
+    the columns never enters."""
     if t.dim() != 2:
         raise ValueError(f"{name} must be 2-D, got shape {tuple(t.shape)}")
-    ok = (t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1]
-          and t.shape[1] % 4 == 0 and t.data_ptr() % 16 == 0)
-    return t if ok else _pad_cols(t, (t.shape[1] + 3) // 4 * 4)
+    ok = (t.stride(1) == 1 and t.stride(0) % q == 0 and t.stride(0) >= t.shape[1]
+          and t.shape[1] % q == 0 and t.data_ptr() % 16 == 0)
+    return t if ok else _pad_cols(t, -(-t.shape[1] // q) * q)
 
 
 def _pad_cols(t: torch.Tensor, dp: int) -> torch.Tensor:
-    """A fresh contiguous float32 copy of the 2-D ``t`` with its columns zero-padded to dp."""
-    out = torch.zeros((t.shape[0], dp), dtype=torch.float32, device=t.device)
+    """A fresh contiguous copy of the 2-D ``t``, in its dtype, with its columns zero-padded to dp."""
+    out = torch.zeros((t.shape[0], dp), dtype=t.dtype, device=t.device)
     out[:, :t.shape[1]] = t
     return out
+
+
+# dtype -> (element-type code, elements of the narrowest load group, base alignment in bytes)
+# of the samples that the packed entry points read in place (csrc/sample_src.hpp kSampleRules)
+_SAMPLE_TYPES = {torch.float32: ("DEIG_F32", 4, 16), torch.bfloat16: ("DEIG_BF16", 8, 16),
+                 torch.uint8: ("DEIG_U8", 4, 4)}
+
+
+def _in_place(X: torch.Tensor) -> bool:
+    """Can a packed entry point read the 2-D float32 / bfloat16 / uint8 X where it lies?"""
+    _, q, align = _SAMPLE_TYPES[X.dtype]
+    d = X.shape[1]
+    ldx = _ld(X, 0, d)
+    return (d >= q and d % q == 0 and X.stride(1) == 1 and ldx >= d and ldx % q == 0
+            and X.data_ptr() % align == 0)
+
+
+def _packed_samples(X, name: str, xname: str, dmin: int = 0):
+    """``(X, xtype, n, d, dp)`` of the samples of a packed entry point (deig_oja_steps_centered,
+    deig_gram_apply, deig_topk_samples): uint8 and bfloat16 samples stay what they are,
+    anything else becomes float32; on the device and read where they lie when strides and
+    alignment allow (``_in_place``, and d >= dmin), otherwise from a zero-padded copy of the
+    SAME dtype with dp columns, dp = d rounded up to the type's load group, at least dmin."""
+    if isinstance(X, torch.Tensor) and X.dtype in (torch.uint8, torch.bfloat16):
+        X = _to_device(X, name)
+    else:
+        X = require_device_tensor(X, name)
+    if X.dim() != 2:
+        raise ValueError(f"{xname} must be 2-D, got shape {tuple(X.shape)}")
+    n, d = X.shape
+    code, q, _ = _SAMPLE_TYPES[X.dtype]
+    dp = max(dmin, -(-d // q) * q)
+    if dp != d or not _in_place(X):
+        X = _pad_cols(X, dp)
+    return X, getattr(_lib, code), n, d, dp
 
 
 def _stack_4(Wt: torch.Tensor, dp: int) -> torch.Tensor:
@@ -268,7 +294,7 @@ def sigma_hat(x: torch.Tensor, alpha: float | None = None,
     n, d = x.shape
     if n == 0:
         return _nan_cov(d, torch.float32, x.device)
-    xx = _rowmajor_4(x, "x")
+    xx = _rowmajor(x, "x")
     dp = xx.shape[1]
     if out is not None and dp == d and out.shape == (d, d) and out.is_contiguous() \
             and out.dtype == torch.float32 and out.device == x.device and d % 4 == 0:
@@ -309,7 +335,7 @@ def sigma_hat_bf16(x: torch.Tensor, alpha: float | None = None,
                          "d % 8 == 0")
     if n == 0:
         return _nan_cov(d, torch.float32, x.device)
-    xx = _rowmajor_8_bf16(x, "x")
+    xx = _rowmajor(x, "x", 8)
     dp = xx.shape[1]
     S = out if direct else torch.empty((dp, dp), dtype=torch.float32, device=x.device)
     _call(x.device, "deig_syrk_bf16",
@@ -429,10 +455,7 @@ def _u8_samples(x, mode: str, name: str):
         x = torch.as_tensor(x)
     if x.dtype != torch.uint8:
         raise ValueError(f"{name} needs uint8 samples, got {x.dtype}")
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
-    if x.device.type != "cuda":
-        x = x.to(torch.device("cuda", torch.cuda.current_device()))
+    x = _to_device(x, name)
     if mode == "auto":
         mode = "gray" if x.dim() == 4 else "raw"
     if mode not in _lib.U8_MODES:
@@ -461,15 +484,18 @@ def _u8_samples(x, mode: str, name: str):
 
 
 def _pad_vector(v, d: int, dp: int, device, name: str):
-    """(d,) float64 vector on the device, zero-padded to dp entries (None stays None)."""
+    """(d,) float64 vector on the device with unit stride and 8-byte alignment, zero-padded to
+    dp entries: a padded column stages fl32(0 - 0) = 0 (None stays None)."""
     if v is None:
         return None
     v = torch.as_tensor(v).to(device=device, dtype=torch.float64).reshape(-1)
     if v.numel() != d:
         raise ValueError(f"{name} must hold d = {d} numbers, got {v.numel()}")
     if dp != d:
-        v = torch.cat([v, torch.zeros(dp - d, dtype=torch.float64, device=device)])
-    return v.contiguous()
+        v = torch.cat([v, v.new_zeros(dp - d)])
+    elif v.stride(0) != 1 or v.data_ptr() % 8:
+        v = v.clone()
+    return v
 
 
 def _transform_operands(W, d, dp, mean, dev, wname: str, multiple: int = 4):
@@ -796,44 +822,17 @@ def projavg_topk(Wt: torch.Tensor, k: int, scale: float, *, p: int | None = None
 
 # ---------------------------------------------------------------- covariance-free route
 def _sample_operands(X, center, name: str):
-    """``(X, xtype, n, d, dp, center)`` of a covariance-free call: float32, bfloat16 and 2-D
-    uint8 samples are read where they lie when strides and alignment allow (the rules of
-    ``_oja_in_place``, and d >= 16), otherwise from a zero-padded copy of the SAME dtype with
-    dp columns; ``center`` as float64 on the device, zero-padded alike (a padded column stages
-    fl32(0 - 0) = 0).  float64 samples raise: the route's products are float32."""
-    if isinstance(X, torch.Tensor) and X.dtype == torch.float64:
+    """``(X, xtype, n, d, dp, center)`` of a covariance-free call: the samples as
+    ``_packed_samples`` gives them with d >= 16, ``center`` as ``_pad_vector`` does.  float64
+    samples raise: the route's products are float32."""
+    if str(getattr(X, "dtype", "")).endswith("float64"):
         raise TypeError(f"{name}: float64 samples are not supported by the covariance-free route; "
                         "use the explicit route (sigma_hat / sigma_hat_centered + topk_eigh), which "
                         "reads float64 in double")
-    if isinstance(X, torch.Tensor) and X.dtype in (torch.uint8, torch.bfloat16):
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
-        if X.device.type != "cuda":
-            X = X.to(torch.device("cuda", torch.cuda.current_device()))
-    else:
-        if not isinstance(X, torch.Tensor) and getattr(X, "dtype", None) == "float64":
-            raise TypeError(f"{name}: float64 samples are not supported by the covariance-free "
-                            "route; use the explicit route (sigma_hat + topk_eigh)")
-        X = require_device_tensor(X, name)
-    if X.dim() != 2 or X.shape[0] < 1:
+    X, xtype, n, d, dp = _packed_samples(X, name, "X", 16)
+    if n < 1:
         raise ValueError(f"{name}: X must be 2-D with at least one row, got shape {tuple(X.shape)}")
-    n, d = X.shape
-    code, q, _ = _OJA_XTYPES[X.dtype]
-    dp = max(16, (d + q - 1) // q * q)
-    if dp != d or not _oja_in_place(X):
-        Xp = torch.zeros((n, dp), dtype=X.dtype, device=X.device)
-        Xp[:, :d] = X
-        X = Xp
-    c = None
-    if center is not None:
-        c = torch.as_tensor(center).to(device=X.device, dtype=torch.float64).reshape(-1)
-        if c.numel() != d:
-            raise ValueError(f"center must have d = {d} entries, got {c.numel()}")
-        if dp != d:
-            c = torch.cat([c, c.new_zeros(dp - d)])
-        elif c.stride(0) != 1 or c.data_ptr() % 8:
-            c = c.clone()
-    return X, getattr(_lib, code), n, d, dp, c
+    return X, xtype, n, d, dp, _pad_vector(center, d, dp, X.device, "center")
 
 
 def gram_apply(X: torch.Tensor, Q: torch.Tensor, center=None, alpha: float | None = None) -> torch.Tensor:
@@ -1010,13 +1009,10 @@ def oja_step(Xb: torch.Tensor, V: torch.Tensor, eta: float, center=None) -> torc
     """
     if center is not None:
         return _oja_steps_centered(Xb, V, eta, None, 1, center, "oja_step", "Xb")
-    xb8 = _oja_u8_samples(Xb, V, "auto", Xb.shape[0] if isinstance(Xb, torch.Tensor) else 0, "oja_step")
-    if xb8 is not None:
-        return _oja_steps_centered(xb8, V, eta, None, 1, None, "oja_step", "Xb")
-    xb16 = _oja_bf16_samples(Xb, "auto", "oja_step")
-    if xb16 is not None:
-        return _oja_steps_bf16(xb16, V, eta, xb16.shape[0], 1, 1, "Xb")
-    Xb = _rowmajor_4(require_device_tensor(Xb, "oja_step"), "Xb")
+    xb = _oja_reads_in_place(Xb, V, "auto", Xb.shape[0] if isinstance(Xb, torch.Tensor) else 0, "oja_step")
+    if xb is not None:
+        return _oja_steps_centered(xb, V, eta, None, 1, None, "oja_step", "Xb")
+    Xb = _rowmajor(require_device_tensor(Xb, "oja_step"), "Xb")
     b, d = Xb.shape
     k = _oja_basis(V, Xb, "Xb")
     _call(Xb.device, "deig_oja_step_f32",
@@ -1035,112 +1031,45 @@ def _oja_basis(V: torch.Tensor, X: torch.Tensor, xname: str) -> int:
     return V.shape[1]
 
 
-def _oja_bf16_samples(X, algo: str, name: str) -> torch.Tensor | None:
-    """The bfloat16 samples of an Oja call as ``deig_oja_steps_bf16`` takes them, or None
-    when the call goes the float32 route: not bfloat16, ``algo="resident"``, or a view the
-    entry point cannot read in place (not 2-D with unit column stride, d % 8 != 0, a row
-    stride % 8 != 0, a base that is not 16-byte aligned)."""
-    if not isinstance(X, torch.Tensor) or X.dtype != torch.bfloat16 or algo not in ("auto", "two_pass"):
+def _oja_reads_in_place(X, V, algo: str, batch: int, name: str) -> torch.Tensor | None:
+    """The bfloat16 or uint8 samples of an uncentred Oja call, on the device, where the
+    two-pass route (deig_oja_steps_centered with a NULL centre) can read them in place; None
+    when the call keeps the float32 route: another dtype, ``algo="resident"``, a view the
+    entry point cannot read in place (``_in_place``), or - uint8 only - ``algo="auto"`` at the
+    resident-eligible shape (whose bits are the resident kernel's, not the two-pass
+    kernels')."""
+    if not isinstance(X, torch.Tensor) or X.dtype not in (torch.bfloat16, torch.uint8) \
+            or algo not in ("auto", "two_pass") or X.dim() != 2 or X.shape[0] < 1:
         return None
-    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 8 or X.shape[1] % 8:
-        return None
-    X = bf16_device_tensor(X, name)  # a host tensor is copied over as bfloat16
-    ldx = _ld(X, 0, X.shape[1])
-    if X.stride(1) != 1 or ldx % 8 or ldx < X.shape[1] or X.data_ptr() % 16:
-        return None
-    return X
-
-
-def _oja_steps_bf16(X: torch.Tensor, V: torch.Tensor, eta: float, b: int, nb: int, orth_every: int,
-                    xname: str) -> torch.Tensor:
-    """nb batches of b rows of the bfloat16 X (``_oja_bf16_samples``) through
-    deig_oja_steps_bf16: X with its own row stride, no copy, no ``oja_check``."""
-    d = X.shape[1]
-    k = _oja_basis(V, X, xname)
-    _call(X.device, "deig_oja_steps_bf16",
-          (X.data_ptr(), nb, b, d, _ld(X, 0, d), eta, V.data_ptr(), k, _ld(V, 1, d), int(orth_every)),
-          "deig_oja_workspace", (b, d, k))
-    return V
-
-
-# dtype -> (element-type code, elements of the narrowest load group, base alignment in bytes)
-# of the samples deig_oja_steps_centered reads in place
-_OJA_XTYPES = {torch.float32: ("DEIG_F32", 4, 16), torch.bfloat16: ("DEIG_BF16", 8, 16),
-               torch.uint8: ("DEIG_U8", 4, 4)}
-
-
-def _oja_in_place(X: torch.Tensor) -> bool:
-    """Can deig_oja_steps_centered read the 2-D float32 / bfloat16 / uint8 X where it lies?"""
-    _, q, align = _OJA_XTYPES[X.dtype]
-    d = X.shape[1]
-    ldx = _ld(X, 0, d)
-    return (d >= q and d % q == 0 and X.stride(1) == 1 and ldx >= d and ldx % q == 0
-            and X.data_ptr() % align == 0)
-
-
-def _oja_u8_samples(X, V, algo: str, batch: int, name: str) -> torch.Tensor | None:
-    """The uint8 samples of an uncentred Oja call as deig_oja_steps_centered reads them in
-    place, or None when the call keeps the float32 route: not uint8, ``algo="resident"``, a
-    view the entry point cannot read in place, or ``algo="auto"`` at the resident-eligible
-    shape (whose bits are the resident kernel's, not the two-pass kernels')."""
-    if not isinstance(X, torch.Tensor) or X.dtype != torch.uint8 or algo not in ("auto", "two_pass"):
-        return None
-    if X.dim() != 2 or X.shape[0] < 1 or not isinstance(V, torch.Tensor) or V.dim() != 2:
-        return None
-    d = X.shape[1]
-    if algo == "auto" and batch == 4096 and d % 512 == 0 and 0 < d <= 3072 and V.shape[1] <= 32:
-        return None
-    if X.device.type != "cuda":
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
-        X = X.to(torch.device("cuda", torch.cuda.current_device()))
-    return X if _oja_in_place(X) else None
+    if X.dtype == torch.uint8:
+        if not isinstance(V, torch.Tensor) or V.dim() != 2:
+            return None
+        d = X.shape[1]
+        if algo == "auto" and batch == 4096 and d % 512 == 0 and 0 < d <= 3072 and V.shape[1] <= 32:
+            return None
+    X = _to_device(X, name)
+    return X if _in_place(X) else None
 
 
 def _oja_steps_centered(X, V: torch.Tensor, eta: float, batch, orth_every: int, center, name: str,
                         xname: str) -> torch.Tensor:
     """Batches of ``batch`` rows (None: all of X is one batch) through
-    deig_oja_steps_centered: uint8 and bfloat16 samples stay what they are, anything else
-    becomes float32; a view the entry point cannot read in place is copied into a
-    zero-padded tensor of the SAME dtype (with ``center`` and V zero-padded to its columns:
-    a padded column stages fl32(0 - 0) = 0 and its row of V stays zero).  No ``oja_check``:
-    the route cannot time out, and the call stays asynchronous."""
-    if isinstance(X, torch.Tensor) and X.dtype in (torch.uint8, torch.bfloat16):
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{name}: needs a ROCm GPU; there is no CPU fallback")
-        if X.device.type != "cuda":
-            X = X.to(torch.device("cuda", torch.cuda.current_device()))
-    else:
-        X = require_device_tensor(X, name)
-    if X.dim() != 2:
-        raise ValueError(f"{xname} must be 2-D, got shape {tuple(X.shape)}")
-    n, d = X.shape
+    deig_oja_steps_centered on the samples as ``_packed_samples`` gives them, with ``center``
+    and V zero-padded to a padded copy's columns (its row of V stays zero).  No
+    ``oja_check``: the route cannot time out, and the call stays asynchronous."""
+    X, xtype, n, d, dp = _packed_samples(X, name, xname)
     b = n if batch is None else int(batch)
     nb = n // b if b > 0 else 0
     if nb < 1:
         raise ValueError(f"need at least one full batch of {batch} rows, got {n} rows")
-    code, q, _ = _OJA_XTYPES[X.dtype]
-    dp = (d + q - 1) // q * q
-    if not _oja_in_place(X):
-        Xp = torch.zeros((n, dp), dtype=X.dtype, device=X.device)
-        Xp[:, :d] = X
-        X = Xp
-    c = None
-    if center is not None:
-        c = torch.as_tensor(center).to(device=X.device, dtype=torch.float64).reshape(-1)
-        if c.numel() != d:
-            raise ValueError(f"center must have d = {d} entries, got {c.numel()}")
-        if dp != d:
-            c = torch.cat([c, c.new_zeros(dp - d)])
-        elif c.stride(0) != 1 or c.data_ptr() % 8:
-            c = c.clone()
+    c = _pad_vector(center, d, dp, X.device, "center")
     Vc = V
     if dp != d and isinstance(V, torch.Tensor) and V.dim() == 2 and V.shape[0] == d:
         Vc = torch.zeros((V.shape[1], dp), dtype=V.dtype, device=V.device).t()
         Vc[:d] = V
     k = _oja_basis(Vc, X, xname)
     _call(X.device, "deig_oja_steps_centered",
-          (X.data_ptr(), getattr(_lib, code), nb, b, dp, _ld(X, 0, dp), _ptr(c), eta, Vc.data_ptr(), k,
+          (X.data_ptr(), xtype, nb, b, dp, _ld(X, 0, dp), _ptr(c), eta, Vc.data_ptr(), k,
            _ld(Vc, 1, dp), int(orth_every)),
           "deig_oja_workspace", (b, dp, k))
     if Vc is not V:
@@ -1175,7 +1104,8 @@ def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
     before any other op on this thread's stream (they share the workspace that holds
     the timeout word).  Returns V.
 
-    bfloat16 samples are consumed as bfloat16 (include/deig.h deig_oja_steps_bf16: the
+    bfloat16 samples are consumed as bfloat16 (include/deig.h deig_oja_steps_centered without
+    a centre, which is deig_oja_steps_bf16 bit for bit: the
     two-pass kernels with the sample as the MFMA operand, two products per fragment pair
     instead of three, no float32 copy; the bits of ``algo="two_pass"`` on ``X.float()``)
     when ``algo`` is "auto" or "two_pass" and X is a 2-D view with unit column stride,
@@ -1226,13 +1156,10 @@ def oja_steps(X: torch.Tensor, V: torch.Tensor, eta: float, batch: int,
             raise ValueError("oja_steps: there is no centred resident kernel; use algo='auto' or "
                              "'two_pass' with a center")
         return _oja_steps_centered(X, V, eta, b, orth_every, center, "oja_steps", "X")
-    x8 = _oja_u8_samples(X, V, algo, b, "oja_steps")
-    if x8 is not None and 0 < b <= x8.shape[0]:
-        return _oja_steps_centered(x8, V, eta, b, orth_every, None, "oja_steps", "X")
-    x16 = _oja_bf16_samples(X, algo, "oja_steps")
-    if x16 is not None and 0 < b <= x16.shape[0]:
-        return _oja_steps_bf16(x16, V, eta, b, x16.shape[0] // b, orth_every, "X")
-    X = _rowmajor_4(require_device_tensor(X, "oja_steps"), "X")
+    xp = _oja_reads_in_place(X, V, algo, b, "oja_steps")
+    if xp is not None and 0 < b <= xp.shape[0]:
+        return _oja_steps_centered(xp, V, eta, b, orth_every, None, "oja_steps", "X")
+    X = _rowmajor(require_device_tensor(X, "oja_steps"), "X")
     n, d = X.shape
     nb = n // b if b > 0 else 0
     if nb < 1:
@@ -1344,7 +1271,7 @@ def sym_power(S: torch.Tensor, Q: torch.Tensor, cs: torch.Tensor, steps: int,
 # ---------------------------------------------------------------- projection
 def project(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     """Y = X W  (NB:345 ``X @ matrix_w``): X (n, d) row-major, W (d, k) any layout."""
-    X = _rowmajor_4(require_device_tensor(X, "project"), "X")
+    X = _rowmajor(require_device_tensor(X, "project"), "X")
     n, dp = X.shape
     dev = X.device
     W, _, k = _transform_operands(W, None, dp, None, dev, "matrix_w")
@@ -1370,39 +1297,24 @@ def pca_transform(X: torch.Tensor, W: torch.Tensor, mean: torch.Tensor | None = 
     the tuple (Y[, residual][, energy])."""
     if not isinstance(X, torch.Tensor):
         X = torch.as_tensor(X)
-    if X.dtype == torch.bfloat16:
-        return _pca_transform_bf16(X, W, mean, residual, energy)
+    bf16 = X.dtype == torch.bfloat16
     mu = None
     if mean is not None:
         mu = torch.as_tensor(mean).to(dtype=torch.float64).reshape(-1)
     if X.dtype == torch.float64 and mu is not None:
         X = require_device_tensor(X, "pca_transform", keep_f64=True)
         X, mu = (X - mu.to(X.device)).to(torch.float32), None
-    X = _rowmajor_4(require_device_tensor(X, "pca_transform"), "X")
+    q = 8 if bf16 else 4
+    X = _rowmajor(_to_device(X, "pca_transform") if bf16 else require_device_tensor(X, "pca_transform"), "X", q)
     n, dp = X.shape
     dev = X.device
-    W, mu, k = _transform_operands(W, None, dp, mu, dev, "W")
+    W, mu, k = _transform_operands(W, None, dp, mu, dev, "W", q)
     Y, res, en = _transform_buffers(n, k, dev, residual, energy)
     if n > 0:
-        _call(dev, "deig_pca_transform_f32",
+        _call(dev, "deig_pca_transform_bf16" if bf16 else "deig_pca_transform_f32",
               (X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp),
                Y.data_ptr(), _ld(Y, 0, k), _ptr(res), _ptr(en)),
-              "deig_pca_transform_workspace", (n, dp, k))
-    return _transform_result(Y, res, en)
-
-
-def _pca_transform_bf16(X, W, mean, residual: bool, energy: bool):
-    """``pca_transform`` of bfloat16 samples (include/deig.h deig_pca_transform_bf16)."""
-    X = _rowmajor_8_bf16(bf16_device_tensor(X, "pca_transform"), "X")
-    n, dp = X.shape
-    dev = X.device
-    W, mu, k = _transform_operands(W, None, dp, mean, dev, "W", multiple=8)
-    Y, res, en = _transform_buffers(n, k, dev, residual, energy)
-    if n > 0:
-        _call(dev, "deig_pca_transform_bf16",
-              (X.data_ptr(), n, dp, _ld(X, 0, dp), _ptr(mu), W.data_ptr(), k, _ld(W, 1, dp),
-               Y.data_ptr(), _ld(Y, 0, k), _ptr(res), _ptr(en)),
-              "deig_pca_transform_bf16_workspace", (n, dp, k))
+              "deig_pca_transform_bf16_workspace" if bf16 else "deig_pca_transform_workspace", (n, dp, k))
     return _transform_result(Y, res, en)
 
 

@@ -79,12 +79,19 @@ def test_transform_argument_rules():
     def call(n=8, d=16, ldx=16, k=4, ldw=16, ldy=4, X=PTR, W=PTR, Y=PTR):
         return L.deig_pca_transform_bf16(X, n, d, ldx, None, W, k, ldw, Y, ldy, None, None, None, 0,
                                          None)
-    for kw, word in [(dict(k=0), "k=0"), (dict(k=257, ldy=257), "k=257"),
-                     (dict(d=12), "multiple of 8"), (dict(ldx=20), "ldx must be"),
-                     (dict(ldx=8), "ldx must be"), (dict(Y=None), "at least one output"),
-                     (dict(X=None), "must not be NULL"), (dict(n=0), "n must be >= 1")]:
+    # the full text of deig_last_error(), as a build of the commit before csrc/sample_src.hpp
+    # reported it
+    for kw, msg in [(dict(k=0), "k=0 must be in 1..256"), (dict(k=257, ldy=257), "k=257 must be in 1..256"),
+                    (dict(d=12), "d must be a multiple of 8 (got 12)"),
+                    (dict(d=12, ldx=8), "d must be a multiple of 8 (got 12)"),  # two rules: d first
+                    (dict(ldx=20), "ldx must be >= d and a multiple of 8 elements"),
+                    (dict(ldx=8), "ldx must be >= d and a multiple of 8 elements"),
+                    (dict(Y=None), "need at least one output (Y, resid, energy)"),
+                    (dict(X=None), "X (16-byte aligned) and W must not be NULL"),
+                    (dict(X=PTR + 2), "X (16-byte aligned) and W must not be NULL"),
+                    (dict(n=0), "n must be >= 1 (got 0)")]:
         assert call(**kw) == _lib.DEIG_EINVAL, kw
-        assert word in _lib.last_error(), _lib.last_error()
+        assert _lib.last_error() == "pca_transform_bf16: " + msg
     assert call() == _lib.DEIG_EWORKSPACE
     for k in (1, 64, 256):
         kp = (k + 15) // 16 * 16

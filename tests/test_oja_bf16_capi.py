@@ -28,24 +28,51 @@ def _oja(X=PTR, nb=2, b=64, d=16, ldx=16, V=PTR, k=4, ldv=16, orth_every=1, ws=N
                                           ws_bytes, None)
 
 
-@pytest.mark.parametrize("kw,word", [
-    (dict(d=12, ldx=16, ldv=16), "d must be a multiple of 8"),
-    (dict(ldx=8), "ldx must be >= d"),
-    (dict(ldx=20), "ldx must be a multiple of 8"),
-    (dict(X=None), "must not be NULL"),
-    (dict(V=None), "must not be NULL"),
-    (dict(X=PTR + 2), "16-byte aligned"),
-    (dict(k=0), "1 <= k <= min(64, d)"),
-    (dict(k=65, d=128, ldx=128, ldv=128), "1 <= k <= min(64, d)"),
-    (dict(k=17), "1 <= k <= min(64, d)"),
-    (dict(nb=0), "nb must be >= 1"),
-    (dict(b=0), "b must be >= 1"),
-    (dict(orth_every=0), "orth_every must be >= 1"),
-    (dict(ldv=8), "ldv must be >= d"),
-])
-def test_argument_rules(kw, word):
+# (arguments, the rule's words, the full text of deig_last_error() as a build of the commit
+# before csrc/sample_src.hpp reported it)
+RULES = [
+    (dict(d=12, ldx=16, ldv=16), "d must be a multiple of 8",
+     "oja_bf16: d must be a multiple of 8, at least 8 (got 12)"),
+    (dict(ldx=8), "ldx must be >= d",
+     "oja_bf16: ldx must be >= d"),
+    (dict(ldx=20), "ldx must be a multiple of 8",
+     "oja_bf16: ldx must be a multiple of 8 elements"),
+    (dict(X=None), "must not be NULL",
+     "oja_bf16: X and V must not be NULL"),
+    (dict(V=None), "must not be NULL",
+     "oja_bf16: X and V must not be NULL"),
+    (dict(X=PTR + 2), "16-byte aligned",
+     "oja_bf16: X must be 16-byte aligned"),
+    (dict(k=0), "1 <= k <= min(64, d)",
+     "oja_bf16: need 1 <= k <= min(64, d) (got k=0, d=16)"),
+    (dict(k=65, d=128, ldx=128, ldv=128), "1 <= k <= min(64, d)",
+     "oja_bf16: need 1 <= k <= min(64, d) (got k=65, d=128)"),
+    (dict(k=17), "1 <= k <= min(64, d)",
+     "oja_bf16: need 1 <= k <= min(64, d) (got k=17, d=16)"),
+    (dict(nb=0), "nb must be >= 1",
+     "oja_bf16: nb must be >= 1 (got 0)"),
+    (dict(b=0), "b must be >= 1",
+     "oja_bf16: b must be >= 1 (got 0)"),
+    (dict(orth_every=0), "orth_every must be >= 1",
+     "oja_bf16: orth_every must be >= 1 (got 0)"),
+    (dict(ldv=8), "ldv must be >= d",
+     "oja_bf16: ldv must be >= d"),
+    # two rules broken at once: d is tested first
+    (dict(d=12, ldx=8), "d must be a multiple of 8",
+     "oja_bf16: d must be a multiple of 8, at least 8 (got 12)"),
+]
+
+
+def _ids(rules):
+    """pytest's own ids of these tables when they held (arguments, word) pairs: kept, so that
+    every case keeps its name."""
+    return [f"kw{i}-{word}" for i, (_, word, _) in enumerate(rules)]
+
+
+@pytest.mark.parametrize("kw,word,msg", RULES, ids=_ids(RULES))
+def test_argument_rules(kw, word, msg):
     assert _oja(**kw) == _lib.DEIG_EINVAL
-    assert word in _lib.last_error(), _lib.last_error()
+    assert word in msg and _lib.last_error() == msg
 
 
 def test_short_or_null_workspace():

@@ -34,35 +34,77 @@ def _oja(xtype=F32, X=PTR, nb=2, b=64, d=16, ldx=16, center=PTR, V=PTR, k=4, ldv
                                               orth_every, ws, ws_bytes, None)
 
 
-@pytest.mark.parametrize("kw,word", [
-    (dict(xtype=F64), "xtype must be"),
-    (dict(xtype=7), "xtype must be"),
-    (dict(xtype=F32, d=14), "d must be a multiple of 4"),
-    (dict(xtype=U8, d=14), "d must be a multiple of 4"),
-    (dict(xtype=BF16, d=12), "d must be a multiple of 8"),
-    (dict(xtype=F32, ldx=12), "ldx must be >= d"),
-    (dict(xtype=BF16, ldx=8), "ldx must be >= d"),
-    (dict(xtype=U8, ldx=12), "ldx must be >= d"),
-    (dict(xtype=F32, ldx=18), "ldx must be a multiple of 4"),
-    (dict(xtype=U8, ldx=18), "ldx must be a multiple of 4"),
-    (dict(xtype=BF16, ldx=20), "ldx must be a multiple of 8"),
-    (dict(k=0), "1 <= k <= min(64, d)"),
-    (dict(k=65, d=128, ldx=128, ldv=128), "1 <= k <= min(64, d)"),
-    (dict(k=17), "1 <= k <= min(64, d)"),
-    (dict(orth_every=0), "orth_every must be >= 1"),
-    (dict(nb=0), "nb must be >= 1"),
-    (dict(b=0), "b must be >= 1"),
-    (dict(ldv=8), "ldv must be >= d"),
-    (dict(X=None), "must not be NULL"),
-    (dict(V=None), "must not be NULL"),
-    (dict(xtype=F32, X=PTR + 4), "16-byte aligned"),
-    (dict(xtype=BF16, X=PTR + 2), "16-byte aligned"),
-    (dict(xtype=U8, X=PTR + 2), "4-byte aligned"),
-    (dict(center=PTR + 4), "center must be aligned"),
-])
-def test_argument_rules(kw, word):
+# (arguments, the rule's words, the full text of deig_last_error() as a build of the commit
+# before csrc/sample_src.hpp reported it)
+RULES = [
+    (dict(xtype=F64), "xtype must be",
+     "oja_centered: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got 1)"),
+    (dict(xtype=7), "xtype must be",
+     "oja_centered: xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got 7)"),
+    (dict(xtype=F32, d=14), "d must be a multiple of 4",
+     "oja_centered: d must be a multiple of 4, at least 4 (got 14)"),
+    (dict(xtype=U8, d=14), "d must be a multiple of 4",
+     "oja_centered: d must be a multiple of 4, at least 4 (got 14)"),
+    (dict(xtype=BF16, d=12), "d must be a multiple of 8",
+     "oja_centered: d must be a multiple of 8, at least 8 (got 12)"),
+    (dict(xtype=F32, ldx=12), "ldx must be >= d",
+     "oja_centered: ldx must be >= d"),
+    (dict(xtype=BF16, ldx=8), "ldx must be >= d",
+     "oja_centered: ldx must be >= d"),
+    (dict(xtype=U8, ldx=12), "ldx must be >= d",
+     "oja_centered: ldx must be >= d"),
+    (dict(xtype=F32, ldx=18), "ldx must be a multiple of 4",
+     "oja_centered: ldx must be a multiple of 4 elements"),
+    (dict(xtype=U8, ldx=18), "ldx must be a multiple of 4",
+     "oja_centered: ldx must be a multiple of 4 elements"),
+    (dict(xtype=BF16, ldx=20), "ldx must be a multiple of 8",
+     "oja_centered: ldx must be a multiple of 8 elements"),
+    (dict(k=0), "1 <= k <= min(64, d)",
+     "oja_centered: need 1 <= k <= min(64, d) (got k=0, d=16)"),
+    (dict(k=65, d=128, ldx=128, ldv=128), "1 <= k <= min(64, d)",
+     "oja_centered: need 1 <= k <= min(64, d) (got k=65, d=128)"),
+    (dict(k=17), "1 <= k <= min(64, d)",
+     "oja_centered: need 1 <= k <= min(64, d) (got k=17, d=16)"),
+    (dict(orth_every=0), "orth_every must be >= 1",
+     "oja_centered: orth_every must be >= 1 (got 0)"),
+    (dict(nb=0), "nb must be >= 1",
+     "oja_centered: nb must be >= 1 (got 0)"),
+    (dict(b=0), "b must be >= 1",
+     "oja_centered: b must be >= 1 (got 0)"),
+    (dict(ldv=8), "ldv must be >= d",
+     "oja_centered: ldv must be >= d"),
+    (dict(X=None), "must not be NULL",
+     "oja_centered: X and V must not be NULL"),
+    (dict(V=None), "must not be NULL",
+     "oja_centered: X and V must not be NULL"),
+    (dict(xtype=F32, X=PTR + 4), "16-byte aligned",
+     "oja_centered: X must be 16-byte aligned"),
+    (dict(xtype=BF16, X=PTR + 2), "16-byte aligned",
+     "oja_centered: X must be 16-byte aligned"),
+    (dict(xtype=U8, X=PTR + 2), "4-byte aligned",
+     "oja_centered: X must be 4-byte aligned"),
+    (dict(center=PTR + 4), "center must be aligned",
+     "oja_centered: center must be aligned to its element size"),
+    # two rules broken at once: d is tested first
+    (dict(xtype=F32, d=14, ldx=12), "d must be a multiple of 4",
+     "oja_centered: d must be a multiple of 4, at least 4 (got 14)"),
+    (dict(xtype=U8, d=14, ldx=12), "d must be a multiple of 4",
+     "oja_centered: d must be a multiple of 4, at least 4 (got 14)"),
+    (dict(xtype=BF16, d=12, ldx=8), "d must be a multiple of 8",
+     "oja_centered: d must be a multiple of 8, at least 8 (got 12)"),
+]
+
+
+def _ids(rules):
+    """pytest's own ids of these tables when they held (arguments, word) pairs: kept, so that
+    every case keeps its name."""
+    return [f"kw{i}-{word}" for i, (_, word, _) in enumerate(rules)]
+
+
+@pytest.mark.parametrize("kw,word,msg", RULES, ids=_ids(RULES))
+def test_argument_rules(kw, word, msg):
     assert _oja(**kw) == _lib.DEIG_EINVAL
-    assert word in _lib.last_error(), _lib.last_error()
+    assert word in msg and _lib.last_error() == msg
 
 
 @pytest.mark.parametrize("xtype", [F32, BF16, U8])

@@ -44,64 +44,126 @@ def _topk(xtype=F32, X=PTR, n=10, d=32, ldx=32, center=PTR, k=4, p=16, max_sweep
                                         None, ws, ws_bytes, None)
 
 
+# (arguments, the rule's words, the full text of deig_last_error() behind the entry point's name
+# as a build of the commit before csrc/sample_src.hpp reported it); SAMPLE_RULES and TWO_RULES
+# are gram_apply_check's, which both entry points run first
 SAMPLE_RULES = [
-    (dict(xtype=F64), "xtype must be"),
-    (dict(xtype=7), "xtype must be"),
-    (dict(xtype=F32, d=30), "d must be a multiple of 4"),
-    (dict(xtype=U8, d=30), "d must be a multiple of 4"),
-    (dict(xtype=BF16, d=28), "d must be a multiple of 8"),
-    (dict(xtype=F32, ldx=28), "ldx must be >= d"),
-    (dict(xtype=BF16, ldx=24), "ldx must be >= d"),
-    (dict(xtype=U8, ldx=28), "ldx must be >= d"),
-    (dict(xtype=F32, ldx=34), "ldx must be a multiple of 4"),
-    (dict(xtype=U8, ldx=34), "ldx must be a multiple of 4"),
-    (dict(xtype=BF16, ldx=36), "ldx must be a multiple of 8"),
-    (dict(d=12, ldx=12), "d must be >= 16"),
-    (dict(n=0), "n must be >= 1"),
-    (dict(X=None), "must not be NULL"),
-    (dict(xtype=F32, X=PTR + 4), "16-byte aligned"),
-    (dict(xtype=BF16, X=PTR + 2), "16-byte aligned"),
-    (dict(xtype=U8, X=PTR + 2), "4-byte aligned"),
-    (dict(center=PTR + 4), "center must be aligned"),
+    (dict(xtype=F64), "xtype must be",
+     "xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got 1)"),
+    (dict(xtype=7), "xtype must be",
+     "xtype must be DEIG_F32, DEIG_BF16 or DEIG_U8 (got 7)"),
+    (dict(xtype=F32, d=30), "d must be a multiple of 4",
+     "d must be a multiple of 4 (got 30)"),
+    (dict(xtype=U8, d=30), "d must be a multiple of 4",
+     "d must be a multiple of 4 (got 30)"),
+    (dict(xtype=BF16, d=28), "d must be a multiple of 8",
+     "d must be a multiple of 8 (got 28)"),
+    (dict(xtype=F32, ldx=28), "ldx must be >= d",
+     "ldx must be >= d"),
+    (dict(xtype=BF16, ldx=24), "ldx must be >= d",
+     "ldx must be >= d"),
+    (dict(xtype=U8, ldx=28), "ldx must be >= d",
+     "ldx must be >= d"),
+    (dict(xtype=F32, ldx=34), "ldx must be a multiple of 4",
+     "ldx must be a multiple of 4 elements"),
+    (dict(xtype=U8, ldx=34), "ldx must be a multiple of 4",
+     "ldx must be a multiple of 4 elements"),
+    (dict(xtype=BF16, ldx=36), "ldx must be a multiple of 8",
+     "ldx must be a multiple of 8 elements"),
+    (dict(d=12, ldx=12), "d must be >= 16",
+     "d must be >= 16 (got 12)"),
+    (dict(n=0), "n must be >= 1",
+     "n must be >= 1 (got 0)"),
+    (dict(X=None), "must not be NULL",
+     "X must not be NULL"),
+    (dict(xtype=F32, X=PTR + 4), "16-byte aligned",
+     "X must be 16-byte aligned"),
+    (dict(xtype=BF16, X=PTR + 2), "16-byte aligned",
+     "X must be 16-byte aligned"),
+    (dict(xtype=U8, X=PTR + 2), "4-byte aligned",
+     "X must be 4-byte aligned"),
+    (dict(center=PTR + 4), "center must be aligned",
+     "center must be aligned to its element size"),
 ]
 
 
-@pytest.mark.parametrize("kw,word", SAMPLE_RULES + [
-    (dict(p=24, ldq=24, ldy=24), "p must be a multiple of 16"),
-    (dict(p=0), "p must be a multiple of 16"),
-    (dict(p=144, d=256, ldx=256, ldq=144, ldy=144), "p must be a multiple of 16"),
-    (dict(Q=None), "must not be NULL"),
-    (dict(Y=None), "must not be NULL"),
-    (dict(Q=PTR + 4), "16-byte aligned"),
-    (dict(Y=PTR + 8), "16-byte aligned"),
-    (dict(ldq=12), "ldq must be >= p"),
-    (dict(ldq=18), "ldq must be >= p and a multiple of 4"),
-    (dict(ldy=12), "ldy must be >= p"),
-    (dict(ldy=18), "ldy must be >= p and a multiple of 4"),
-])
-def test_gram_apply_argument_rules(kw, word):
+GRAM_RULES = [
+    (dict(p=24, ldq=24, ldy=24), "p must be a multiple of 16",
+     "p must be a multiple of 16 in 16..128 (got 24)"),
+    (dict(p=0), "p must be a multiple of 16",
+     "p must be a multiple of 16 in 16..128 (got 0)"),
+    (dict(p=144, d=256, ldx=256, ldq=144, ldy=144), "p must be a multiple of 16",
+     "p must be a multiple of 16 in 16..128 (got 144)"),
+    (dict(Q=None), "must not be NULL",
+     "Q and Y must not be NULL"),
+    (dict(Y=None), "must not be NULL",
+     "Q and Y must not be NULL"),
+    (dict(Q=PTR + 4), "16-byte aligned",
+     "Q and Y must be 16-byte aligned"),
+    (dict(Y=PTR + 8), "16-byte aligned",
+     "Q and Y must be 16-byte aligned"),
+    (dict(ldq=12), "ldq must be >= p",
+     "ldq must be >= p and a multiple of 4"),
+    (dict(ldq=18), "ldq must be >= p and a multiple of 4",
+     "ldq must be >= p and a multiple of 4"),
+    (dict(ldy=12), "ldy must be >= p",
+     "ldy must be >= p and a multiple of 4"),
+    (dict(ldy=18), "ldy must be >= p and a multiple of 4",
+     "ldy must be >= p and a multiple of 4"),
+]
+TOPK_RULES = [
+    (dict(k=0), "1 <= k <= min(128, d)",
+     "need 1 <= k <= min(128, d) (k=0, d=32)"),
+    (dict(k=33, p=48), "1 <= k <= min(128, d)",
+     "need 1 <= k <= min(128, d) (k=33, d=32)"),
+    (dict(k=129, p=128, d=256, ldx=256, ldv=256), "1 <= k <= min(128, d)",
+     "need 1 <= k <= min(128, d) (k=129, d=256)"),
+    (dict(p=24), "p must be a multiple of 16",
+     "p must be a multiple of 16 in 16..128 (got 24)"),
+    (dict(p=0), "p must be a multiple of 16",
+     "p must be a multiple of 16 in 16..128 (got 0)"),
+    (dict(p=144, d=256, ldx=256, ldv=256), "p must be a multiple of 16",
+     "p must be a multiple of 16 in 16..128 (got 144)"),
+    (dict(k=20, p=16), "k <= p <= d",
+     "the subspace needs k <= p <= d (k=20, p=16, d=32)"),
+    (dict(p=48), "k <= p <= d",
+     "the subspace needs k <= p <= d (k=4, p=48, d=32)"),
+    (dict(V=None), "must not be NULL",
+     "V and evals must not be NULL, ldv >= d"),
+    (dict(evals=None), "must not be NULL",
+     "V and evals must not be NULL, ldv >= d"),
+    (dict(ldv=16), "ldv >= d",
+     "V and evals must not be NULL, ldv >= d"),
+    (dict(max_sweeps=0), "max_sweeps must be >= 1",
+     "max_sweeps must be >= 1"),
+    (dict(k0=2, Q0=None), "warm start",
+     "bad warm start (k0=2, p=16)"),
+]
+TWO_RULES = [  # two rules broken at once: d is tested first
+    (dict(xtype=F32, d=30, ldx=28), "d must be a multiple of 4", "d must be a multiple of 4 (got 30)"),
+    (dict(xtype=U8, d=30, ldx=28), "d must be a multiple of 4", "d must be a multiple of 4 (got 30)"),
+    (dict(xtype=BF16, d=28, ldx=24), "d must be a multiple of 8", "d must be a multiple of 8 (got 28)"),
+]
+
+
+def _ids(rules):
+    """pytest's own ids of these tables when they held (arguments, word) pairs: kept, so that
+    every case keeps its name."""
+    return [f"kw{i}-{word}" for i, (_, word, _) in enumerate(rules)]
+
+
+@pytest.mark.parametrize("kw,word,msg", SAMPLE_RULES + GRAM_RULES + TWO_RULES,
+                         ids=_ids(SAMPLE_RULES + GRAM_RULES + TWO_RULES))
+def test_gram_apply_argument_rules(kw, word, msg):
     assert _gram(**kw) == _lib.DEIG_EINVAL
-    assert word in _lib.last_error(), _lib.last_error()
+    assert word in msg and _lib.last_error() == "gram_apply: " + msg
 
 
-@pytest.mark.parametrize("kw,word", SAMPLE_RULES + [
-    (dict(k=0), "1 <= k <= min(128, d)"),
-    (dict(k=33, p=48), "1 <= k <= min(128, d)"),
-    (dict(k=129, p=128, d=256, ldx=256, ldv=256), "1 <= k <= min(128, d)"),
-    (dict(p=24), "p must be a multiple of 16"),
-    (dict(p=0), "p must be a multiple of 16"),
-    (dict(p=144, d=256, ldx=256, ldv=256), "p must be a multiple of 16"),
-    (dict(k=20, p=16), "k <= p <= d"),
-    (dict(p=48), "k <= p <= d"),
-    (dict(V=None), "must not be NULL"),
-    (dict(evals=None), "must not be NULL"),
-    (dict(ldv=16), "ldv >= d"),
-    (dict(max_sweeps=0), "max_sweeps must be >= 1"),
-    (dict(k0=2, Q0=None), "warm start"),
-])
-def test_topk_samples_argument_rules(kw, word):
+@pytest.mark.parametrize("kw,word,msg", SAMPLE_RULES + TOPK_RULES + TWO_RULES,
+                         ids=_ids(SAMPLE_RULES + TOPK_RULES + TWO_RULES))
+def test_topk_samples_argument_rules(kw, word, msg):
     assert _topk(**kw) == _lib.DEIG_EINVAL
-    assert word in _lib.last_error(), _lib.last_error()
+    assert word in msg and _lib.last_error() == "topk_samples: " + msg
 
 
 @pytest.mark.parametrize("xtype", [F32, BF16, U8])

@@ -13,7 +13,9 @@ in-tree distributed_eigenspaces_amd/libdeig.so.
   python tools/ab.py transform KIND REPS N D K LIB [LIB ...]   # fused PCA transform, KIND as cov
   python tools/ab.py sweep REPS D P MODE LIB [LIB ...]     # solver sweep chain, us per sweep
                                                            # MODE half | bf16x3 | bf16x5 | bf16x6
-  python tools/ab.py oja   REPS ORTH LIB [LIB ...]         # config-4 Oja, us per batch
+  python tools/ab.py oja   [KIND] REPS ORTH LIB [LIB ...]  # config-4 Oja, us per batch; KIND f32 (default)
+                                                           # | bf16 | u8, each optionally +c (a centre)
+  python tools/ab.py gram  KIND REPS N D P LIB [LIB ...]   # deig_gram_apply, KIND as oja, us per apply
   python tools/ab.py rr    [LIB ...]                       # RR small-solve phases (DEIG_DEBUG)
   python tools/ab.py tests TAG LIB [LIB ...] [-- PYTEST ARGS]   # GPU suite per build
 """
@@ -300,12 +302,43 @@ def ab_sweep(reps, d, p, mode, paths):
 
 
 # ---------------------------------------------------------------- oja
-def ab_oja(reps, orth, paths):
+SAMPLE_KINDS = {"f32": "DEIG_F32", "bf16": "DEIG_BF16", "u8": "DEIG_U8"}
+
+
+def packed_samples(kind, n, d, dev):
+    """(X, xtype, centre, scale): n x d samples of KIND f32 | bf16 | u8 (+c: with their float64
+    column mean as the centre, else None): normal floats, bytes around 128 with a spread of 30;
+    scale: their standard deviation."""
+    import torch
+    from distributed_eigenspaces_amd import _lib
+    base, centred = kind.partition("+")[::2]
+    if base not in SAMPLE_KINDS or centred not in ("", "c"):
+        raise SystemExit(__doc__)
+    g = torch.Generator(device=dev).manual_seed(7)
+    X = torch.empty((n, d), dtype={"f32": torch.float32, "bf16": torch.bfloat16, "u8": torch.uint8}[base], device=dev)
+    for lo in range(0, n, 1 << 14):
+        blk = X[lo:lo + (1 << 14)]
+        r = torch.randn(blk.shape, generator=g, device=dev)
+        blk.copy_(r.mul_(30.0).add_(128.0).clamp_(0, 255) if base == "u8" else r)
+    centre = None
+    if centred:
+        centre = torch.stack([X[lo:lo + (1 << 14)].double().sum(0) for lo in range(0, n, 1 << 14)]).sum(0) / n
+    return X, getattr(_lib, SAMPLE_KINDS[base]), centre, 30.0 if base == "u8" else 1.0
+
+
+def ab_oja(kind, reps, orth, paths):
+    """Config 4's Oja run.  KIND f32: deig_oja_steps_f32 (the library chooses the kernels);
+    bf16: deig_oja_steps_bf16; u8 and every +c: deig_oja_steps_centered."""
     import torch
     libs = load_libs(paths)
     b, d, k, nb = 4096, 3072, 32, 64
     dev = torch.device("cuda", 0)
-    X = torch.randn(nb * b, d, device=dev)
+    if kind == "f32":
+        X, xtype, centre, eta = torch.randn(nb * b, d, device=dev), 0, None, 0.02
+    else:
+        X, xtype, centre, scale = packed_samples(kind, nb * b, d, dev)
+        # a byte's mean taken uncentred dominates the second moment: eta lambda_max about 1
+        eta = 0.02 / scale ** 2 if centre is not None or kind != "u8" else 1.0 / (128.0 ** 2 * d)
     V0 = torch.linalg.qr(torch.randn(d, k, device=dev, dtype=torch.float64))[0].float()
     nbytes = max(L.deig_oja_workspace(b, d, k) for _, L in libs)
     ws = torch.zeros(nbytes // 4 + 64, dtype=torch.float32, device=dev)
@@ -313,19 +346,56 @@ def ab_oja(reps, orth, paths):
 
     def run(path, L):
         V = V0.t().contiguous().t()
+        tail = (ctypes.c_float(eta), V.data_ptr(), k, V.stride(1), orth, ws.data_ptr(), nbytes, None)
         torch.cuda.synchronize()
         e0.record()
-        rc = L.deig_oja_steps_f32(X.data_ptr(), nb, b, d, X.stride(0), ctypes.c_float(0.02), V.data_ptr(),
-                                  k, V.stride(1), orth, ws.data_ptr(), nbytes, None)
+        if kind == "f32":
+            rc = L.deig_oja_steps_f32(X.data_ptr(), nb, b, d, X.stride(0), *tail)
+        elif kind == "bf16":
+            rc = L.deig_oja_steps_bf16(X.data_ptr(), nb, b, d, X.stride(0), *tail)
+        else:
+            rc = L.deig_oja_steps_centered(X.data_ptr(), xtype, nb, b, d, X.stride(0),
+                                           None if centre is None else centre.data_ptr(), *tail)
         e1.record()
         e1.synchronize()
-        assert rc == 0
+        assert rc == 0, L.deig_last_error()
         return e0.elapsed_time(e1) / nb * 1e3, V
 
     times, outs = interleave(libs, reps, run)
     ref = outs[libs[0][0]]
-    report(times, lambda p: torch.equal(outs[p], ref) and bool(torch.isfinite(outs[p]).all()),
-           "us/batch (config 4: 64 x 4096 x 3072, k = 32)")
+    report_json(times, lambda p: torch.equal(outs[p], ref) and bool(torch.isfinite(outs[p]).all()),
+                f"us/batch ({kind}, config 4: 64 x 4096 x 3072, k = 32)", paths,
+                {"op": "oja", "kind": kind, "b": b, "d": d, "k": k, "nb": nb, "orth_every": orth, "reps": reps})
+
+
+# ---------------------------------------------------------------- gram (covariance-free operator)
+def ab_gram(kind, reps, n, d, p, paths):
+    """deig_gram_apply, Y = (1/n) Xc^T (Xc Q), on the recommended workspace; KIND as oja."""
+    import torch
+    libs = load_libs(paths)
+    dev = torch.device("cuda", 0)
+    X, xtype, centre, _ = packed_samples(kind, n, d, dev)
+    Q = torch.randn(d, p, generator=torch.Generator(device=dev).manual_seed(8), device=dev)
+    nbytes = max(L.deig_gram_apply_workspace(n, d, p, xtype) for _, L in libs)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    out = {path: torch.empty(d, p, device=dev) for path, _ in libs}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def run(path, L):
+        torch.cuda.synchronize()
+        e0.record()
+        rc = L.deig_gram_apply(X.data_ptr(), xtype, n, d, X.stride(0), None if centre is None else centre.data_ptr(),
+                               ctypes.c_float(1.0 / n), Q.data_ptr(), p, p, out[path].data_ptr(), p, ws.data_ptr(),
+                               nbytes, None)
+        e1.record()
+        e1.synchronize()
+        assert rc == 0, L.deig_last_error()
+        return e0.elapsed_time(e1) * 1e3, out[path]
+
+    times, outs = interleave(libs, reps, run)
+    ref = outs[libs[0][0]]
+    report_json(times, lambda q: torch.equal(outs[q], ref) and bool(torch.isfinite(outs[q]).all()),
+                f"us ({kind} {n} x {d}, p = {p})", paths, {"op": "gram", "kind": kind, "n": n, "d": d, "p": p, "reps": reps})
 
 
 # ---------------------------------------------------------------- rr phases
@@ -427,7 +497,10 @@ def main(argv):
     elif cmd == "sweep":
         ab_sweep(int(a[0]), int(a[1]), int(a[2]), a[3], a[4:])
     elif cmd == "oja":
-        ab_oja(int(a[0]), int(a[1]), a[2:])
+        kind, a = (a[0], a[1:]) if not a[0].isdigit() else ("f32", a)
+        ab_oja(kind, int(a[0]), int(a[1]), a[2:])
+    elif cmd == "gram":
+        ab_gram(a[0], int(a[1]), int(a[2]), int(a[3]), int(a[4]), a[5:])
     elif cmd == "rr":
         ab_rr(a)
     elif cmd == "tests":
