@@ -8,6 +8,9 @@ Hot path (HIP, gfx950, behind the C ABI in include/deig.h):
   * projavg_topk   - implicit projector-average solve         (distributed.py:126-130, NB:306)
   * topk_samples   - covariance-free worker solve: top-k straight from f32 / bf16 / uint8 rows
   * gram_apply     - its operator, alpha Xc^T (Xc Q), without a d x d matrix
+  * topk_dual      - wide-data worker solve (n <= d): top-k through the n x n Gram matrix of
+                     the samples, finished on topk_samples's operator
+  * gram_outer     - that matrix, alpha Xc Xc^T, on the bf16 MFMA
   * procrustes_average - Procrustes-aligned basis average (one-pass aggregator, no eigensolve)
   * subspace_distance / projector_distance - residual-form sin Theta on the device
   * column_sums / sigma_hat_centered - opt-in centred covariance about a pooled mean
@@ -31,7 +34,7 @@ Drop-in modules: ``distributed`` (Node / SlaveNode / MasterNode / run_* / main),
 compute_segma_hat, online loop).
 """
 from .linalg import (EigResult, column_sums, column_sums_u8, default_subspace,  # noqa: F401
-                     gram_apply, topk_samples, oja_step, oja_steps, pca_transform, pca_transform_u8, procrustes_average,
+                     gram_apply, gram_outer, topk_dual, topk_samples, oja_step, oja_steps, pca_transform, pca_transform_u8, procrustes_average,
                      projavg_topk, projector_distance, sigma_hat, sigma_hat_bf16, sigma_hat_centered,
                      sigma_hat_u8_centered, stack_bases, subspace_distance, sym_apply, sym_power,
                      topk_eigh, topk_eigh_batch)

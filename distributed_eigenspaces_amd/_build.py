@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdeig.so")
 SOURCES = ["capi.hip", "solver.hip", "syrk.hip", "syrk_split.hip", "syrk_u8.hip", "skinny.hip", "rr.hip", "oja.hip",
-           "project.hip", "sweep.hip", "shift.hip", "procrustes.hip", "pca.hip", "pca_u8.hip", "syrk_bf16.hip", "pca_bf16.hip", "gram.hip"]
+           "project.hip", "sweep.hip", "shift.hip", "procrustes.hip", "pca.hip", "pca_u8.hip", "syrk_bf16.hip", "pca_bf16.hip", "gram.hip",
+           "gram_nt.hip"]
 # Per-source extra flags.  sweep.hip: keep the split's scalar f32 subtractions
 # unpacked (v_pk_add_f32 beside MFMAs costs issue cycles, MI355X_MICROARCH.md).
 # pca_bf16.hip: the super-chunk loop of pca_packed_tile.hpp starts on a 64-byte instruction
@@ -25,7 +26,7 @@ SOURCES = ["capi.hip", "solver.hip", "syrk.hip", "syrk_split.hip", "syrk_u8.hip"
 # (profiles/pca_transform_packed_refactor.json).
 EXTRA_FLAGS = {"sweep.hip": ["-fno-slp-vectorize"], "syrk_split.hip": ["-fno-slp-vectorize"],
                "pca_bf16.hip": ["-Xarch_device", "-falign-loops=64"]}
-HEADERS = ["deig_internal.hpp", "sample_src.hpp", "skinny_tile.hpp", "pca_packed_tile.hpp", "syrk_image_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
+HEADERS = ["deig_internal.hpp", "sample_src.hpp", "skinny_tile.hpp", "pca_packed_tile.hpp", "syrk_image_tile.hpp", "syrk_bf16_tile.hpp", "lds_dma.hpp", "bf16_split.hpp", os.path.join("..", "..", "include", "deig.h")]
 # Test-only variant (tests/test_gpu_oja_timeout.py): oja.hip with a zero spin bound, so
 # every resident hand-off times out and the DEIG_ETIMEOUT report can be exercised; the
 # other objects are the shipped library's.

@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
@@ -446,6 +447,151 @@ int deig_topk_samples(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
   pr.evals = evals;
   return solve_lockstep(1, &pr, d, k, p, max_sweeps, tol, ldv, sweeps_out, resid_out, nullptr,
                         make_opts(opts), ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t deig_gram_outer_workspace(int64_t n, int64_t d, int xtype, int centred) {
+  return gram_outer_workspace_bytes(n, d, xtype, centred);
+}
+
+int deig_gram_outer(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                    float alpha, float* K, int64_t ldk, int flags, void* ws, size_t ws_bytes,
+                    void* stream) {
+  g_err[0] = 0;
+  return gram_outer_launch(X, xtype, n, d, ldx, center, alpha, K, ldk, flags, ws, ws_bytes,
+                           (hipStream_t)stream);
+}
+
+// The dual solve's workspace: what outlives a phase (K, then U and lam, then V0) in front, then
+// one region that the phases use in turn - the Gram product, the n x n solve, the
+// back-projection (Zt, Y, split-K slab), the finish.
+namespace {
+struct DualWs {
+  float *K, *U, *lam, *V0, *Zt, *Y, *slab;
+  char* phase;
+  int64_t ldk;
+  int kp, pn;
+  size_t outer_bytes, solve_bytes, finish_bytes, phase_bytes, total;
+};
+DualWs carve_dual(void* ws, int64_t n, int64_t d, int k, int p, int xtype, const deig_solver_opts* opts) {
+  DualWs w{};
+  w.ldk = (n + 3) / 4 * 4;
+  w.kp = (k + 15) / 16 * 16;
+  w.pn = default_subspace(n, k);
+  Carve c(ws, 0);
+  w.K = c.take<float>((size_t)n * w.ldk);
+  w.U = c.take<float>((size_t)n * k);
+  w.lam = c.take<float>((size_t)k);
+  w.V0 = c.take<float>((size_t)d * k);
+  w.phase = c.take<char>(0);
+  const size_t front = c.off;
+  w.outer_bytes = gram_outer_workspace_bytes(n, d, xtype, 1);
+  w.solve_bytes = solver_workspace_bytes(n, k, w.pn, false, 0, make_opts(opts), DEIG_F32);
+  w.finish_bytes = solver_workspace_bytes(d, k, p, true, 0, make_opts(opts), DEIG_F32, n, xtype);
+  Carve b(w.phase, 0);
+  w.Zt = b.take<float>((size_t)n * w.kp);
+  w.Y = b.take<float>((size_t)d * w.kp);
+  const int ks = gram_tn_split(d, n);
+  w.slab = b.take<float>(ks > 1 ? (size_t)ks * d * w.kp : 0);
+  w.phase_bytes = std::max(std::max(w.outer_bytes, w.solve_bytes), std::max(w.finish_bytes, b.off));
+  w.total = front + align_up(w.phase_bytes, 256);
+  return w;
+}
+bool topk_dual_shape_ok(int64_t n, int64_t d, int k, int p, int xtype) {
+  return topk_samples_shape_ok(n, d, k, p, xtype) && n <= 32768 && k <= n;
+}
+}  // namespace
+
+size_t deig_topk_dual_workspace(int64_t n, int64_t d, int k, int p, int xtype,
+                                const deig_solver_opts* opts) {
+  if (check_opts(opts) || !topk_dual_shape_ok(n, d, k, p, xtype)) return 0;
+  const DualWs w = carve_dual(nullptr, n, d, k, p, xtype, opts);
+  if (!w.outer_bytes || !w.solve_bytes || !w.finish_bytes) return 0;
+  return w.total;
+}
+
+int deig_topk_dual(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                   float scale, int k, int p, int max_sweeps, float tol, float* V, int64_t ldv,
+                   float* evals, int* sweeps_out, float* resid_out, const deig_solver_opts* opts,
+                   void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const char* what = "topk_dual";
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = check_opts(opts)) return rc;
+  if (int rc = gram_apply_check(X, xtype, n, d, ldx, center, what)) return rc;
+  if (n > 32768)
+    return fail(DEIG_EINVAL, "%s: n must be <= 32768 (got %lld): the n x n Gram matrix is the route for "
+                             "n <= d; use deig_topk_samples", what, (long long)n);
+  if (k < 1 || k > 128 || k > n || k > d)
+    return fail(DEIG_EINVAL, "%s: need 1 <= k <= min(128, n, d) (k=%d, n=%lld, d=%lld)", what, k,
+                (long long)n, (long long)d);
+  if (p < 16 || p > 128 || p % 16 != 0)
+    return fail(DEIG_EINVAL, "%s: p must be a multiple of 16 in 16..128 (got %d)", what, p);
+  if (p < k || p > d)
+    return fail(DEIG_EINVAL, "%s: the subspace needs k <= p <= d (k=%d, p=%d, d=%lld)", what, k, p,
+                (long long)d);
+  if (max_sweeps < 1) return fail(DEIG_EINVAL, "%s: max_sweeps must be >= 1", what);
+  if (!V || !evals || ldv < d) return fail(DEIG_EINVAL, "%s: V and evals must not be NULL, ldv >= d", what);
+  if (!(scale > 0.f)) return fail(DEIG_EINVAL, "%s: scale must be > 0", what);
+  const size_t need = deig_topk_dual_workspace(n, d, k, p, xtype, opts);
+  if (!ws || ws_bytes < need || !need)
+    return fail(DEIG_EWORKSPACE, "%s: workspace %zu bytes < required %zu", what, ws ? ws_bytes : (size_t)0,
+                need);
+  const DualWs w = carve_dual(ws, n, d, k, p, xtype, opts);
+  const Opts o = make_opts(opts);
+  // 1. K = scale Xc Xc^T
+  if (int rc = gram_outer_launch(X, xtype, n, d, ldx, center, scale, w.K, w.ldk, 0, w.phase, w.phase_bytes,
+                                 st))
+    return rc;
+  // 2. its top-k pairs (U n x k column-major, lam ascending) by the explicit solver; a start
+  // that has not converged is still a start
+  {
+    SolveProblem pr{};
+    pr.op.implicit = false;
+    pr.op.S = w.K;
+    pr.op.stype = DEIG_F32;
+    pr.op.lds = w.ldk;
+    pr.V = w.U;
+    pr.evals = w.lam;
+    const int rc = solve_lockstep(1, &pr, n, k, w.pn, max_sweeps, tol, n, nullptr, nullptr, nullptr, o,
+                                  w.phase, w.phase_bytes, st);
+    if (rc != DEIG_OK && rc != DEIG_NOT_CONVERGED) return rc;
+  }
+  // 3. the usable pairs: lam_j > n 2^-23 lam_max (ascending: the last k0 columns); K is
+  // fp32-grade, what lies below that is rounding
+  float lam_h[128];
+  DEIG_HIP_CHECK(hipMemcpyAsync(lam_h, w.lam, sizeof(float) * k, hipMemcpyDeviceToHost, st));
+  DEIG_HIP_CHECK(hipStreamSynchronize(st));
+  int k0 = 0;
+  const float lmax = lam_h[k - 1];
+  if (lmax > 0.f) {
+    const float thr = (float)n * 1.1920929e-7f * lmax;
+    while (k0 < k && lam_h[k - 1 - k0] > thr) ++k0;
+  }
+  if (k0 > 0) {
+    // Zt = U diag(sqrt(scale / lam)), then 4. V0 = Xc^T Zt: unit columns, v = Xc^T u sqrt(scale / lam)
+    if (int rc = dual_scale_launch(w.U, n, w.lam, k, w.kp, k0, scale, n, w.Zt, st)) return rc;
+    if (int rc = gram_tn_launch(X, xtype, n, d, ldx, center, w.Zt, w.kp, 1.f, w.Y, w.kp, w.slab, st))
+      return rc;
+    if (int rc = dual_cols_launch(w.Y, w.kp, d, k - k0, k0, w.V0, st)) return rc;
+  }
+  // 5. the finish on the real operator: deig_topk_samples from Q0 = V0
+  g_err[0] = 0;
+  SolveProblem pr{};
+  pr.op.implicit = true;
+  pr.op.stype = DEIG_F32;
+  pr.op.X = X;
+  pr.op.xtype = xtype;
+  pr.op.n = n;
+  pr.op.ldx = ldx;
+  pr.op.center = center;
+  pr.op.scale = scale;
+  pr.Q0 = k0 ? w.V0 : nullptr;
+  pr.k0 = k0;
+  pr.ldq0 = d;
+  pr.V = V;
+  pr.evals = evals;
+  return solve_lockstep(1, &pr, d, k, p, max_sweeps, tol, ldv, sweeps_out, resid_out, nullptr, o, w.phase,
+                        w.phase_bytes, st);
 }
 
 size_t deig_procrustes_workspace(int64_t d, int64_t mk, int k) {

@@ -174,6 +174,28 @@ int gram_apply_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
                       float alpha, const float* Q, int p, int64_t ldq, float* Y, int64_t ldy, void* ws,
                       size_t ws_bytes, hipStream_t stream);
 
+// Its second product alone (the back-projection of the dual solve): Y (d x p row-major, ldy)
+// = alpha Xc^T Zt over all n rows, Zt n x p row-major with row stride p; slab holds
+// gram_tn_split(d, n) * d * p floats when the split is > 1.
+int gram_tn_split(int64_t d, int64_t n);
+int gram_tn_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                   const float* Zt, int p, float alpha, float* Y, int64_t ldy, float* slab,
+                   hipStream_t stream);
+
+// The sample-space Gram K = alpha Xc Xc^T (n x n, both triangles) of the dual solve
+// (gram_nt.hip); X, xtype, center as for gram_apply_launch, n <= 32768, flags 0.  Runs in
+// feature chunks sized by the workspace.
+size_t gram_outer_workspace_bytes(int64_t n, int64_t d, int xtype, int centred);
+int gram_outer_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                      float alpha, float* K, int64_t ldk, int flags, void* ws, size_t ws_bytes,
+                      hipStream_t stream);
+// The dual solve's relayouts: Zt[r][j] = U[r][j] sqrt(scale / lam[j]) for the last k0 of U's k
+// columns (U n x k column-major, ldu), zero elsewhere, n x kp row-major; and V0 (d x k0
+// column-major, ld d) = columns c0 .. c0 + k0 - 1 of the d x kp row-major Y (k0 >= 1).
+int dual_scale_launch(const float* U, int64_t ldu, const float* lam, int k, int kp, int k0, float scale,
+                      int64_t n, float* Zt, hipStream_t stream);
+int dual_cols_launch(const float* Y, int kp, int64_t d, int c0, int k0, float* V0, hipStream_t stream);
+
 // bf16x6 symmetric sweep (sweep.hip): Y = alpha * S Q, S symmetric d x d
 // row-major, Q d x p (ldq), Y d x p (ldy), p % 16 == 0, p <= 128.
 size_t sweep_workspace_bytes(int64_t d, int p);

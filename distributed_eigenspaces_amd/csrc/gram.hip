@@ -242,6 +242,19 @@ int launch_tn(const void* X, int64_t ldx, const double* center, const float* Zt,
 
 }  // namespace
 
+// The second product alone, for the dual solve's back-projection (capi.hip deig_topk_dual):
+// Y (d x p row-major, ldy) = alpha Xc^T Zt for all n rows of X at once, Zt n x p row-major
+// with row stride p.  slab: gram_tn_split(d, n) * d * p floats when that is > 1.
+int gram_tn_split(int64_t d, int64_t n) { return gram_ks(d, n); }
+
+int gram_tn_launch(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx, const double* center,
+                   const float* Zt, int p, float alpha, float* Y, int64_t ldy, float* slab,
+                   hipStream_t st) {
+  return dispatch_sample(xtype, [&](auto s) {
+    return launch_tn<decltype(s)>(X, ldx, center, Zt, Y, ldy, d, n, p, alpha, 0.f, slab, gram_ks(d, n), st);
+  });
+}
+
 // Rows per chunk that the workspace query recommends: all of them, up to 2^20 (Zt is then at
 // most 512 MB at p = 128).  Measured (profiles/topk_samples.json, 65536 x 16384, p = 80): a
 // chunk small enough for the 256 MB last-level cache does NOT make the second read of X

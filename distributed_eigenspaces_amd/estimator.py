@@ -45,6 +45,14 @@ uint8 shards go through as raw bytes, uncentred or with ``center=True, u8_mode="
 implicit, so the solver does not deflate a dominant mean direction: uncentred data with a
 large mean should use ``center=True`` or the explicit route.
 
+``covariance="dual"`` (opt-in) is the wide-data worker route: every logical worker is
+``linalg.topk_dual`` on its shard - the n_i x n_i sample-space Gram matrix on the bf16 MFMA,
+its top-k, a back-projection and a finish on the same implicit operator as ``"free"``.  It is
+meant for shards with n_i <= d and needs n_i <= 32768 and k <= n_i.  Everything else is as for
+``"free"``: the serial worker loop, the same centring and pooled-mean plumbing, float32,
+bfloat16 or raw uint8 samples, no ``u8_mode="gray"``, no float64.  No automatic choice
+between the routes is made.
+
 The collective layer only uses ``torch.distributed`` with tensors on the rank's
 device, so it runs on ``gloo`` with CPU tensors too (multi-process tests); the
 per-worker compute is injectable for those tests and defaults to the GPU ops.
@@ -64,7 +72,7 @@ __all__ = ["shard_ranges", "rank_shards", "EstimatorResult", "DistributedEigensp
 
 
 AGGREGATES = ("projector", "procrustes")
-COVARIANCES = ("explicit", "free")
+COVARIANCES = ("explicit", "free", "dual")
 
 
 def shard_ranges(n_rows: int, batches_number: int):
@@ -159,6 +167,12 @@ def _gpu_worker_free(x: torch.Tensor, k: int, center=None, u8_mode=None, **kw):
     return r.V, r.evals, r.sweeps
 
 
+def _gpu_worker_dual(x: torch.Tensor, k: int, center=None, u8_mode=None, **kw):
+    """The wide-data worker: top-k through the shard's n x n Gram matrix (uint8: raw bytes)."""
+    r = linalg.topk_dual(x, k, center=center, **kw)
+    return r.V, r.evals, r.sweeps
+
+
 class DistributedEigenspaceEstimator:
     def __init__(self, k: int, workers_per_rank: int = 1, server_rank: int = 0, group=None,
                  worker_fn=None, solver_kw=None, concurrent_workers: bool = False,
@@ -168,13 +182,14 @@ class DistributedEigenspaceEstimator:
             raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
         if covariance not in COVARIANCES:
             raise ValueError(f"covariance must be one of {COVARIANCES}, got {covariance!r}")
-        if covariance == "free" and u8_mode == "gray":
-            raise ValueError("covariance='free' reads uint8 samples as raw bytes only: "
+        if covariance != "explicit" and u8_mode == "gray":
+            raise ValueError(f"covariance={covariance!r} reads uint8 samples as raw bytes only: "
                              "u8_mode='gray' needs covariance='explicit'")
         # "explicit" (default): sigma_hat* + topk_eigh per worker; "free": linalg.topk_samples
-        # on the shard's rows, no d x d covariance, serial worker loop.
+        # on the shard's rows, no d x d covariance, serial worker loop; "dual": linalg.topk_dual
+        # on them, the same loop.
         self.covariance = covariance
-        free = covariance == "free"
+        free = covariance != "explicit"
         # "projector" (default, the reference's server): top-k of the projector average;
         # "procrustes": Procrustes-aligned average of the bases, reference V_1.
         self.aggregator = aggregate
@@ -191,7 +206,7 @@ class DistributedEigenspaceEstimator:
         self.batched = bool(batched_workers) and worker_fn is None and not self.concurrent and not free
         self.server_rank = server_rank
         self.group = group
-        self.worker_fn = worker_fn or (_gpu_worker_free if free else _gpu_worker)
+        self.worker_fn = worker_fn or {"free": _gpu_worker_free, "dual": _gpu_worker_dual}.get(covariance, _gpu_worker)
         self.solver_kw = dict(solver_kw or {})
         # center (opt-in): the eigenspace of the covariance about the pooled mean of all
         # ranks' rows; the default stays the reference's uncentred second moment.

@@ -28,7 +28,7 @@ __all__ = [
     "column_sums", "sigma_hat_centered", "pca_transform",
     "column_sums_u8", "sigma_hat_u8_centered", "pca_transform_u8",
     "sigma_hat_bf16", "bf16_device_tensor",
-    "gram_apply", "topk_samples",
+    "gram_apply", "topk_samples", "gram_outer", "topk_dual",
 ]
 
 DEFAULT_TOL = 1e-6
@@ -886,6 +886,50 @@ def topk_samples(X: torch.Tensor, k: int, center=None, alpha: float | None = Non
                 ctypes.byref(sweeps), ctypes.byref(resid), o),
                "deig_topk_samples_workspace", (n, dp, k, pp, xtype, o))
     res = _finish(rc, V, evals, sweeps, resid, "deig_topk_samples")
+    if dp != d:
+        res.V = res.V[:d].t().contiguous().t()
+    return res
+
+
+# ---------------------------------------------------------------- wide-data (dual) route
+def gram_outer(X: torch.Tensor, center=None, alpha: float | None = None) -> torch.Tensor:
+    """``alpha * Xc Xc^T``, the (n, n) float32 sample-space Gram matrix of the n x d samples X
+    (float32, bfloat16 or uint8 raw bytes) about ``center`` (d values, taken in float64; None:
+    no centring) on the bf16 MFMA (include/deig.h deig_gram_outer): bit-exactly symmetric,
+    n <= 32768; alpha defaults to 1/n.  The matrix of ``topk_dual``."""
+    X, xtype, n, d, dp, c = _sample_operands(X, center, "gram_outer")
+    ldk = -(-n // 4) * 4
+    K = torch.empty((n, ldk), dtype=torch.float32, device=X.device)
+    _call(X.device, "deig_gram_outer",
+          (X.data_ptr(), xtype, n, dp, _ld(X, 0, dp), _ptr(c), _alpha(alpha, n), K.data_ptr(), ldk, 0),
+          "deig_gram_outer_workspace", (n, dp, xtype, int(c is not None)))
+    return K[:, :n] if ldk != n else K
+
+
+def topk_dual(X: torch.Tensor, k: int, center=None, alpha: float | None = None, *,
+              p: int | None = None, tol: float = DEFAULT_TOL, max_sweeps: int = DEFAULT_MAX_SWEEPS,
+              opts: "_lib.SolverOpts | None" = None) -> EigResult:
+    """Top-k eigenpairs (ascending) of ``alpha * Xc^T Xc`` through the n x n Gram matrix of the
+    samples: the wide-data worker route (include/deig.h deig_topk_dual) for n <= d, n <= 32768.
+    ``gram_outer`` on the bf16 MFMA, its top-k by the explicit solver, one back-projection, and
+    a finish by ``topk_samples``'s solver from that start - so the result, its stopping rule
+    and ``sweeps`` (the finish's) are ``topk_samples``'s, and so is its caveat: a dominant mean
+    direction is not deflated, centre such data.  Arguments as for ``topk_samples``;
+    1 <= k <= min(128, n, d)."""
+    if len(getattr(X, "shape", ())) == 2 and int(k) > X.shape[0]:  # before X moves anywhere
+        raise ValueError(f"topk_dual: k={int(k)} exceeds the n={X.shape[0]} rows of X (the Gram "
+                         "matrix is n x n)")
+    X, xtype, n, d, dp, c = _sample_operands(X, center, "topk_dual")
+    k = _check_k(k, d)
+    pp = int(p) if p else default_subspace(dp, k)
+    o = ctypes.byref(opts if opts is not None else _lib.solver_opts())
+    V, evals, sweeps, resid = _solver_outputs(dp, k, X.device)
+    rc = _call(X.device, "deig_topk_dual",
+               (X.data_ptr(), xtype, n, dp, _ld(X, 0, dp), _ptr(c), _alpha(alpha, n), k, pp,
+                int(max_sweeps), tol, V.data_ptr(), dp, evals.data_ptr(), ctypes.byref(sweeps),
+                ctypes.byref(resid), o),
+               "deig_topk_dual_workspace", (n, dp, k, pp, xtype, o))
+    res = _finish(rc, V, evals, sweeps, resid, "deig_topk_dual")
     if dp != d:
         res.V = res.V[:d].t().contiguous().t()
     return res

@@ -59,12 +59,13 @@ class PCA:
             raise ValueError(f"u8_mode must be None, 'raw' or 'gray', got {u8_mode!r}")
         if covariance not in COVARIANCES:
             raise ValueError(f"covariance must be one of {COVARIANCES}, got {covariance!r}")
-        if covariance == "free" and u8_mode == "gray":
-            raise ValueError("covariance='free' reads uint8 samples as raw bytes only: "
+        if covariance != "explicit" and u8_mode == "gray":
+            raise ValueError(f"covariance={covariance!r} reads uint8 samples as raw bytes only: "
                              "u8_mode='gray' needs covariance='explicit'")
         self.u8_mode = u8_mode
-        # the estimator's worker route: "explicit" covariances (default) or "free"
-        # (linalg.topk_samples on the rows; float32, bfloat16 and raw uint8 samples)
+        # the estimator's worker route: "explicit" covariances (default), "free"
+        # (linalg.topk_samples on the rows; float32, bfloat16 and raw uint8 samples) or "dual"
+        # (linalg.topk_dual on them: the n x n Gram matrix, for shards with n <= d)
         self.covariance = covariance
         self.k = int(k)
         self.wpr = int(workers_per_rank)

@@ -635,6 +635,77 @@ int deig_topk_samples(const void* X, int xtype, int64_t n, int64_t d, int64_t ld
 size_t deig_topk_samples_workspace(int64_t n, int64_t d, int k, int p, int xtype,
                                    const deig_solver_opts* opts);
 
+/* Wide-data worker solve through the sample-space (dual) Gram matrix, for n <= d and d beyond
+ * the covariance routes' reach:
+ *   K = alpha * Xc Xc^T  (n x n),   K u = lambda u   =>   v = Xc^T u * sqrt(alpha / lambda)
+ * is a unit eigenvector of  alpha * Xc^T Xc  with the same lambda.  Xc as for deig_gram_apply:
+ * Xc[r][j] = fl32((double)x_rj - center[j]), formed in double and rounded once where a value
+ * is staged (center == NULL: the exact widening of x).
+ *
+ * deig_gram_outer forms K on the bf16 MFMA.  A prep kernel stages a chunk of features of all
+ * n rows as bf16 pieces in MFMA operand order (no transpose: the inner dimension is the
+ * contiguous one of X): a hi piece bf16(t), round to nearest even, and - for float32 samples
+ * and every centred call, where a staged value can have one - a lo piece bf16(t - hi).
+ * Uncentred bf16 and uint8 samples are their own hi piece.  The product kernel runs the
+ * 128 x 128 tile loop of deig_syrk_bf16 once (hi hi) or three times into the same fp32
+ * accumulators (hi hi, hi lo, lo hi; lo lo is dropped); no accumulator takes more than 16384
+ * inner elements per pass before it is written out, and the partial slabs are added in a
+ * fixed order.  Every bf16 x bf16 product is exact in fp32, so with u = 2^-24,
+ * gamma_m = m u / (1 - m u) and T the staged matrix, element by element:
+ *   uncentred bf16 / uint8:        |K - K64| <= (gamma_d + 2 u) alpha |T| |T|^T
+ *                                  (exact when every sum_f |t_if t_jf| < 2^24 and alpha is a
+ *                                  power of two);
+ *   float32 and all centred calls: |K - K64| <= (2^-16 + 1.01 gamma_3d + 2 u) alpha |T| |T|^T.
+ * X, xtype, ldx, alignment and center: the rules of deig_gram_apply (n >= 1, d >= 16, d and ldx
+ * multiples of the type's group, DEIG_F64 is DEIG_EINVAL; no element behind column d of a row
+ * and no row behind n is read).  1 <= n <= 32768.  K: n x n fp32 row-major, 16-byte aligned,
+ * ldk >= n, ldk % 4 == 0; both triangles are written, bit-exactly symmetric; nothing behind
+ * column n of a K row is written.  flags must be 0 (reserved for an accumulate bit).
+ * Workspace: deig_gram_outer_workspace(n, d, xtype, centred) (centred: center != NULL) is the
+ * recommended size, all features in one chunk up to 2^19 of them (0 for shapes the call
+ * rejects; it does not decrease in d).  Any workspace of at least
+ * deig_gram_outer_workspace(n, d', xtype, centred) bytes for some d' <= d is accepted and sets
+ * the feature chunk (deig_syrk_bf16's rule with the roles of n and d swapped); the chunks are
+ * added in order.  It may hold anything on entry.
+ * Asynchronous on `stream`: no allocation, no synchronisation, no atomics, no wait between
+ * workgroups; repeated calls give identical bits.  Argument errors are DEIG_EINVAL with a
+ * message naming the rule, a short or NULL workspace is DEIG_EWORKSPACE, both before any GPU
+ * work.
+ *
+ * deig_topk_dual is host composition on that product:
+ *   1. K = scale * Xc Xc^T into the workspace;
+ *   2. (U, lambda): the top-k pairs of K by the explicit solver as deig_topk_sym_ex runs it on
+ *      an n x n fp32 matrix, subspace deig_default_subspace(n, k), the caller's opts, tol and
+ *      max_sweeps (any n >= 1: the solver pads);
+ *   3. the pairs with lambda_j > n 2^-23 lambda_max are kept (k0 of them), their vectors
+ *      scaled by sqrt(scale / lambda_j);
+ *   4. V0 = Xc^T (U diag(sqrt(scale / lambda))) by the second product of deig_gram_apply;
+ *   5. the finish: the solver of deig_topk_samples on the real operator scale * Xc^T Xc, warm
+ *      started with Q0 = V0, k0, and the caller's p, tol, max_sweeps and opts.
+ * Why the finish exists: K is fp32-grade, and the eigenvectors of K carry an error of about
+ * eps lambda_max / lambda_j, amplified again by the back-projection for small lambda_j.  The
+ * dual solve only supplies the start; the outputs, return codes and stopping rule are exactly
+ * deig_topk_samples's:  max_j ||A v_j - lambda_j v_j|| <= tol lambda_max  on A = scale *
+ * Xc^T Xc.  *sweeps_out is the finish's sweep count; DEIG_NOT_CONVERGED from step 2 is not an
+ * error by itself - the finish decides.  The implicit finish inherits deig_topk_samples's
+ * caveat: a dominant mean direction is not deflated, so centre such data (pass `center`).
+ * Rules: X, xtype, n, d, ldx, center as above; 1 <= k <= min(128, n, d); p, V, ldv, evals as for
+ * deig_topk_samples (p % 16 == 0, 16 <= p <= 128, k <= p <= d); scale > 0; max_sweeps >= 1.
+ * n > 32768 is DEIG_EINVAL: deig_topk_samples is the route there.
+ * Workspace: deig_topk_dual_workspace (0 for shapes the call rejects; it does not decrease in
+ * d): K, U and V0, and one region that the five steps use in turn.  The call synchronises
+ * `stream` as the solvers do.  Additive: probe for the symbols, deig_version() is unchanged. */
+int deig_gram_outer(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                    const double* center, float alpha, float* K, int64_t ldk, int flags,
+                    void* ws, size_t ws_bytes, void* stream);
+size_t deig_gram_outer_workspace(int64_t n, int64_t d, int xtype, int centred);
+int deig_topk_dual(const void* X, int xtype, int64_t n, int64_t d, int64_t ldx,
+                   const double* center, float scale, int k, int p, int max_sweeps, float tol,
+                   float* V, int64_t ldv, float* evals, int* sweeps_out, float* resid_out,
+                   const deig_solver_opts* opts, void* ws, size_t ws_bytes, void* stream);
+size_t deig_topk_dual_workspace(int64_t n, int64_t d, int k, int p, int xtype,
+                                const deig_solver_opts* opts);
+
 /* Projection onto an estimated eigenspace: Y = X W.
  * Replaces the notebook's  online_distributed_PCA = lambda X: X @ matrix_w
  * (Online Distributed PCA.ipynb raw line 345).  X: n x d row-major (ldx), W: d x k
